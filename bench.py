@@ -18,11 +18,16 @@ contiguous shards on target boundaries (balanced by predicted advisory rows) and
 per-rank order kernel (per-package lists, CSR) and the exact-size gather of those lists to rank
 0 over RCCL to the step (strong scaling).
 
-Also reported (rank 0): roofline of the match kernels (algorithmic bytes per launch / HIP
-event time, vs the 8 TB/s HBM peak), the end-to-end pipelined pass over PCIe
-(end_to_end: host batch -> GPU -> per-package advisory lists on the host, N = 1), the
-FillInfo and result.Filter legs behind the match, and the oracle CPU baseline on a
-bounded sample (N = 1).
+A plain run sets up, warms up, times the steps and prints the line of the headline figure.
+--dump-outputs DIR then also writes what the last timed step computed (dump_outputs below).
+
+--full adds, on rank 0, every other measurement to the same line: roofline of the match
+kernels (algorithmic bytes per launch / HIP event time, vs the 8 TB/s HBM peak), the
+DetectedVulnerability export, the end-to-end pipelined pass over PCIe (end_to_end: host
+batch -> GPU -> per-package advisory lists on the host, N = 1), the fresh-batch passes, the
+FillInfo and result.Filter legs behind the match, the C1-shaped drop-in latency, the
+`strong` object at N > 1 and the oracle CPU baseline on a bounded sample (N = 1); the
+--no-* options leave single legs out of a --full run.
 """
 import argparse
 import json
@@ -291,6 +296,35 @@ def pmc_traffic(config, workload, variant, src_hash):
         "avg_ns_full_grid": d["avg_ns_full_grid"], "source": f"profiles/pmc_summary_{config}.json", "note": d["note"]}
 
 
+DUMP_ROWS = 1_500_000  # rows of a sampled output file: all of --dump-outputs stays below 64 MB
+
+
+def dump_outputs(d, pairs, first_pkg, n_pkgs, status):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy
+    files in directory d (every value is an integer below 2^53, so float64 is exact):
+      status.npy           [matches, first poisoned package or -1, error bits] (tvm_match_status)
+      matches.npy          [k, 2] (package, advisory) rows of the match list in (package, advisory)
+                           order (tvm_match_fetch); the whole list up to DUMP_ROWS rows, else a
+                           seeded sample of its rows, ascending
+      match_rows.npy       [k] the rows of the list that matches.npy holds
+      package_matches.npy  [m, 2] (package, length of its advisory list) of every package of the
+                           batch up to DUMP_ROWS / 2 packages, else of a seeded sample, ascending
+    Inputs and samples are seeded, so two builds run with the same arguments write comparable files."""
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(0)
+
+    def sample(n, k):
+        return np.arange(n, dtype=np.int64) if n <= k else np.sort(rng.choice(n, size=k, replace=False))
+
+    rows = sample(len(pairs), DUMP_ROWS)
+    pk = sample(n_pkgs, DUMP_ROWS // 2)
+    counts = np.bincount(pairs[:, 0].astype(np.int64) - first_pkg, minlength=n_pkgs)
+    np.save(os.path.join(d, "status.npy"), np.array(status, dtype=np.float64))
+    np.save(os.path.join(d, "matches.npy"), pairs[rows].astype(np.float64))
+    np.save(os.path.join(d, "match_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "package_matches.npy"), np.stack([pk + first_pkg, counts[pk]], axis=1).astype(np.float64))
+
+
 def launch_ranks(n):
     """N ranks of this script through torch.distributed.run on one node (127.0.0.1, a free
     port), one per GPU; returns the launcher's exit status."""
@@ -319,6 +353,11 @@ def main():
     ap.add_argument("--targets", type=int, default=10000)
     ap.add_argument("--pkgs-per-target", type=int, default=400)
     ap.add_argument("--packages", type=int, default=0, help="c3/c4/c5: packages of the global batch")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the line can carry (roofline, vulns, "
+                         "end_to_end, fresh_batch, fill_info, dropin_latency, cpu_baseline; strong at N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: OMP_NUM_THREADS, else os.cpu_count()")
     ap.add_argument("--no-cpu", action="store_true")
@@ -380,7 +419,8 @@ def main():
     log(rank, f"[bench] {wl.name}: db {wl.n_keys} keys, {wl.n_adv} advisories, tables "
               f"{eng.table_bytes()/1e6:.1f} MB ({time.perf_counter()-t0:.1f}s)")
 
-    rows = wl.rows(db)
+    # predicted advisory rows per package: what the strong shards are balanced by
+    rows = wl.rows(db) if args.gather or args.full else None
     sync = torch.cuda.synchronize if torch.cuda.is_available() else (lambda: None)
 
     def measure(strong, primary):
@@ -406,8 +446,9 @@ def main():
             csr = (torch.empty(max(total, 1), dtype=torch.int32, device=gdev),
                    torch.empty(max(n_local, 1), dtype=torch.int32, device=gdev))
             gather = td.CSRGather(cdev)
+        predicted = f", {int(rows[sb:se].sum())} predicted rows" if rows is not None else ""
         log(rank, f"[bench] {'strong' if strong else 'weak'}: shard {sb}..{se} of {wl.n}: {n_local} packages, "
-                  f"{total} matches, {int(rows[sb:se].sum())} predicted rows ({time.perf_counter()-t0:.1f}s)")
+                  f"{total} matches{predicted} ({time.perf_counter()-t0:.1f}s)")
 
         if primary and args.sweep and rank == 0:
             names, v = [], 0
@@ -470,8 +511,9 @@ def main():
                 do_gather()
             sync()
             out["gather_ms"] = td.max_over_ranks(time.perf_counter() - g0, cdev) * 1e3 / args.steps
-        if args.dump_csr:  # the lists as the timed step leaves them at rank 0, for the parity test
-            adv = rend = None
+        dump_dir = args.dump_outputs if primary else None
+        if args.dump_csr or dump_dir:  # the lists as the last timed step leaves them at rank 0
+            adv = rend = pr = None
             if gather is not None:
                 got = do_gather()
                 if rank == 0:
@@ -480,23 +522,33 @@ def main():
                 pr = mb.pairs()
                 adv = pr[:, 1].astype(np.uint32)
                 rend = np.cumsum(np.bincount(pr[:, 0] - sb, minlength=n_local)).astype(np.uint32)
-            if rank == 0:
+            if rank == 0 and args.dump_csr:  # for the parity test
                 path = args.dump_csr if primary else args.dump_csr.replace(".npz", "_strong.npz")
                 np.savez(path, adv=adv, row_end=rend, n_gpus=world)
+            if rank == 0 and dump_dir:
+                if pr is None:  # gathered: the whole global batch's lists, packages from 0
+                    per_pkg = np.diff(rend.astype(np.int64), prepend=0)
+                    pr = np.stack([np.repeat(np.arange(len(rend), dtype=np.uint32), per_pkg), adv], axis=1)
+                    dump_outputs(dump_dir, pr, 0, len(rend), (len(adv), -1, 0))
+                else:
+                    dump_outputs(dump_dir, pr, sb, n_local, mb.status())
         return out
 
     main_run = measure(args.gather, True)
     mb, total, n_local, sb = main_run["mb"], main_run["total"], main_run["n_local"], main_run["sb"]
     wall, n_job, value, gather_ms = main_run["wall"], main_run["n_job"], main_run["value"], main_run["gather_ms"]
     vname = lib().tvm_variant_name(lib().tvm_engine_last_variant(eng.h)).decode()
+    full = args.full  # everything below the timed region, up to the line, is a --full leg
     # kernel-only time of this rank's pass (HIP events on the engine stream) for the roofline
-    kernel_ms = mb.time(args.steps)
-    alg_bytes = mb.algorithmic_bytes()
-    achieved = alg_bytes / (kernel_ms / 1e3) / 1e9
+    kernel_ms = alg_bytes = achieved = None
+    if full:
+        kernel_ms = mb.time(args.steps)
+        alg_bytes = mb.algorithmic_bytes()
+        achieved = alg_bytes / (kernel_ms / 1e3) / 1e9
     # the batch's DetectedVulnerability set (tvm_match_vulns: the drivers' epilogues over every
     # match; Red Hat batches merged per CVE on the device first), host time of the export
     vulns = None
-    if rank == 0:
+    if full and rank == 0:
         t_v = time.perf_counter()
         vs = mb.vulns()  # the first export builds the per-advisory records (once per DB)
         first_ms = (time.perf_counter() - t_v) * 1e3
@@ -517,7 +569,7 @@ def main():
                        "(first_call_ms)"}
         mb.launch(1)
     strong = None
-    if world > 1 and not args.gather:  # north_star's multi-GPU path: one global batch, lists gathered at rank 0
+    if full and world > 1 and not args.gather:  # north_star's multi-GPU path: one global batch, lists gathered at rank 0
         sr = measure(True, False)
         strong = {"packages_per_s": sr["value"], "ms_per_step": sr["wall"] * 1e3 / args.steps,
                   "gather_ms": sr["gather_ms"], "packages": wl.n, "packages_rank0": sr["n_local"],
@@ -545,7 +597,7 @@ def main():
         vs.close()
         return out
 
-    if world == 1 and not args.no_e2e and rank == 0:
+    if full and world == 1 and not args.no_e2e and rank == 0:
         mp = MatchBatch(eng)
         wl.fill(mp)
         mp.pipeline_prepare(match_cap=total, chunk_packages=args.chunk)
@@ -586,7 +638,7 @@ def main():
 
     # ---- fresh batches: each batch built, prepared and matched once (a fleet scan's steady state) ----
     fresh = None
-    if world == 1 and not args.no_e2e and rank == 0:
+    if full and world == 1 and not args.no_e2e and rank == 0:
         runs = []
         for _ in range(6):  # the first warms the block cache (pool.h); the median of the rest is reported
             tb = time.perf_counter()
@@ -619,7 +671,7 @@ def main():
                      outside="build_ms (in packages_per_s_with_build only): the caller adding the batch's packages")
 
     fill = None
-    if rank == 0 and wl.has_vulns and world == 1:
+    if full and rank == 0 and wl.has_vulns and world == 1:
         # Red Hat batches: the driver's per-CVE merge (redhat.go:146-187) on the device, then
         # FillInfo and result.Filter over the MERGED list - the reference's order of work
         mb.launch(1)
@@ -657,7 +709,7 @@ def main():
                                         "matches_per_s": total / (vex_ms / 1e3)}
 
     dropin = None
-    if not args.no_dropin and args.config == "c2" and rank == 0 and world == 1:
+    if full and not args.no_dropin and args.config == "c2" and rank == 0 and world == 1:
         # C1-shaped request through the drop-in per-target path (debian Scanner.Detect,
         # debian.go:57-119): 100 packages of one Debian 12 image, through the C-ABI alone
         import ctypes
@@ -718,14 +770,13 @@ def main():
                                  "calls_sharing_a_launch": st1[2] - st0[2]}}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         # the box's CPU share: OMP_NUM_THREADS is set to it there (os.cpu_count() shows the
         # whole machine, whose other cores belong to other jobs)
         threads = args.cpu_threads or int(os.environ.get("OMP_NUM_THREADS", 0) or 0) or os.cpu_count() or 1
         cpu = wl.cpu_baseline(args.cpu_seconds, threads)
 
     src_hash = kernel_source_hash()
-    traffic, traffic_src = pmc_traffic(args.config, wl.name, vname, src_hash)
     if rank == 0:
         if args.gather:
             par = f"dp{world}: tables replicated, one global batch sharded x{world} on target boundaries by predicted rows"
@@ -752,12 +803,14 @@ def main():
                        "matches_rank0": total,
                        "kernel_variant": vname, "kernel_source": src_hash, "db_keys": wl.n_keys, "db_advisories": wl.n_adv,
                        "platforms": wl.plats, "parallelism": par, "hip_runtime": trivy_amd.runtime_info()},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_from": traffic_src,
-                         "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": kernel_ms,
-                         "achieved_is": "algorithmic bytes (SURVEY §8d, no cache-reuse credit) / kernel time"},
-            "cpu_baseline": cpu,
         }
+        if full:
+            traffic, traffic_src = pmc_traffic(args.config, wl.name, vname, src_hash)
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_from": traffic_src,
+                                "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": kernel_ms,
+                                "achieved_is": "algorithmic bytes (SURVEY §8d, no cache-reuse credit) / kernel time"}
+            line["cpu_baseline"] = cpu
         if gather_ms is not None:
             line["gather_ms"] = gather_ms
         if strong is not None:

@@ -29,7 +29,7 @@ def test_bench_two_ranks_csr_equals_oracle(tmp_path, oracle_built, gather):
     env = dict(os.environ, TVM_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu", "--no-e2e", "--no-fill", "--dump-csr", dump] + flags + (["--gather"] if gather else []),
+                        "--full", "--no-cpu", "--no-e2e", "--no-fill", "--dump-csr", dump] + flags + (["--gather"] if gather else []),
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

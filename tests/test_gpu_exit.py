@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_bench_run_exits_cleanly():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--keys-per-plat", "3000",
-                        "--targets", "200", "--pkgs-per-target", "400", "--steps", "2", "--warmup", "1", "--no-cpu"],
+                        "--targets", "200", "--pkgs-per-target", "400", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
                        cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

@@ -10,9 +10,9 @@ timeout -k 10 700 python -u -m pytest tests/test_gpu_fillinfo.py tests/test_gpu_
   tests/test_gpu_mix.py -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/gpu_tests.log 2>&1 || { tail -60 $OUT/gpu_tests.log; exit 1; }
 tail -2 $OUT/gpu_tests.log
 for c in c2 c5 c3; do
-  timeout -k 10 300 python -u bench.py --config $c --no-cpu --no-e2e > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -30 $OUT/bench_$c.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --config $c --full --no-cpu --no-e2e > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -30 $OUT/bench_$c.err; exit 1; }
 done
-TVM_NO_TILE_ORDER=1 timeout -k 10 300 python -u bench.py --config c3 --no-cpu --no-e2e > $OUT/bench_c3_noorder.json 2> $OUT/bench_c3_noorder.err
+TVM_NO_TILE_ORDER=1 timeout -k 10 300 python -u bench.py --config c3 --full --no-cpu --no-e2e > $OUT/bench_c3_noorder.json 2> $OUT/bench_c3_noorder.err
 python - <<'PY'
 import json, os
 out = os.environ.get("OUT_DIR")

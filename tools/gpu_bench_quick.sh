@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd $R
 export TMPDIR=/tmp
 for c in ${CONFIGS:-c2 c5}; do
-  timeout -k 10 300 python -u bench.py --config $c --no-cpu ${BENCH_ARGS:-} > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+  timeout -k 10 300 python -u bench.py --config $c --full --no-cpu ${BENCH_ARGS:-} > $OUT/bench_$c.json 2> $OUT/bench_$c.err
   cat $OUT/bench_$c.json
 done
 first=$(echo ${CONFIGS:-c2 c5} | cut -d' ' -f1)

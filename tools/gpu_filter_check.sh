@@ -12,7 +12,7 @@ tail -2 $OUT/gpu_tests.log
 cd /tmp
 for c in ${CONFIGS:-c2}; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace_$c -o run --output-format csv -- \
-    python3 -u $R/bench.py --config $c --no-cpu --no-e2e --steps 10 > $OUT/trace_$c.log 2>&1
+    python3 -u $R/bench.py --config $c --full --no-cpu --no-e2e --steps 10 > $OUT/trace_$c.log 2>&1
   f=$(find $OUT/trace_$c -name '*kernel_stats.csv' | head -1)
   python3 $R/tools/kstats.py "$f"
   : <<'PY'

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 cd /tmp
 for d in ${DIAGS:-0 1 2 3}; do
   TVM_FILTER_DIAG=$d timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/d$d -o run --output-format csv -- \
-    python3 -u $R/bench.py --config ${CONFIG:-c2} --no-cpu --no-e2e --steps 5 --warmup 1 > $OUT/d$d.log 2>&1
+    python3 -u $R/bench.py --config ${CONFIG:-c2} --full --no-cpu --no-e2e --steps 5 --warmup 1 > $OUT/d$d.log 2>&1
   f=$(find $OUT/d$d -name "*kernel_stats.csv" | head -1)
   echo "== diag $d"; python3 $R/tools/kstats.py "$f" | grep -i "filter\|vex\|scan"
 done

@@ -7,10 +7,10 @@ OUT=$R/gpurun_out/${TAG:-quick}
 mkdir -p $OUT
 cd $R
 if [ "${MVN:-0}" == 1 ]; then
-  TVM_BENCH_WEIGHTS=0,1,0,0 timeout -k 10 300 python -u bench.py --config c3 --no-cpu --no-e2e --no-fill > $OUT/mvn.json 2> $OUT/mvn.err
+  TVM_BENCH_WEIGHTS=0,1,0,0 timeout -k 10 300 python -u bench.py --full --config c3 --no-cpu --no-e2e --no-fill > $OUT/mvn.json 2> $OUT/mvn.err
 fi
 for c in ${CONFIGS:-c3}; do
-  timeout -k 10 300 python -u bench.py --config $c --no-cpu --no-e2e --no-fill ${BENCH_ARGS:-} > $OUT/$c.json 2> $OUT/$c.err
+  timeout -k 10 300 python -u bench.py --full --config $c --no-cpu --no-e2e --no-fill ${BENCH_ARGS:-} > $OUT/$c.json 2> $OUT/$c.err
 done
 for f in $OUT/*.json; do
   python3 -c "

@@ -16,7 +16,7 @@ done
 cd /tmp
 for c in ${TRACE:-c2}; do
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace_$c -o run --output-format csv -- \
-    python3 -u $R/bench.py --config $c --no-cpu --no-e2e --steps 10 > $OUT/trace_$c.log 2>&1
+    python3 -u $R/bench.py --config $c --full --no-cpu --no-e2e --steps 10 > $OUT/trace_$c.log 2>&1
   f=$(find $OUT/trace_$c -name '*kernel_stats.csv' | head -1)
   cut -d, -f1-4 "$f" | head -24
 done

@@ -18,7 +18,7 @@ if [ "${SKIP_SMOKE:-0}" != 1 ]; then
   tail -1 $OUT/smoke.log
 fi
 for c in ${CONFIGS:-c2}; do
-  timeout -k 10 300 python -u bench.py --config $c --no-cpu ${BENCH_ARGS:-} > $OUT/bench_$c.json 2> $OUT/bench_$c.err \
+  timeout -k 10 300 python -u bench.py --config $c --full --no-cpu ${BENCH_ARGS:-} > $OUT/bench_$c.json 2> $OUT/bench_$c.err \
     || { tail -30 $OUT/bench_$c.err; exit 1; }
   cat $OUT/bench_$c.json
 done

@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/${TAG:-prof}_$CFG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-RUN="--config $CFG $EXTRA --steps 5 --warmup 1 --no-cpu --no-e2e"
+RUN="--config $CFG $EXTRA --steps 5 --warmup 1 --full --no-cpu --no-e2e"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_trace -o run --output-format csv -- python3 $R/bench.py $RUN > $OUT/prof_trace.log 2>&1
 pmc() {  # name, counters...
   local name=$1; shift

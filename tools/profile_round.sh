@@ -17,12 +17,12 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 STEPS=${STEPS:-20}
-SHORT="--config $CFG $EXTRA --steps 5 --warmup 1 --no-cpu --no-e2e --no-fill"
+SHORT="--config $CFG $EXTRA --steps 5 --warmup 1 --full --no-cpu --no-e2e --no-fill"
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  timeout -k 10 500 python3 $R/bench.py --config $CFG $EXTRA --steps $STEPS > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 500 python3 $R/bench.py --config $CFG $EXTRA --steps $STEPS --full > $OUT/bench.json 2> $OUT/bench.err
   cat $OUT/bench.json
 fi
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_trace -o run --output-format csv -- python3 $R/bench.py --config $CFG $EXTRA --steps 10 --warmup 2 --no-cpu > $OUT/prof_trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_trace -o run --output-format csv -- python3 $R/bench.py --config $CFG $EXTRA --steps 10 --warmup 2 --full --no-cpu > $OUT/prof_trace.log 2>&1
 pmc() {  # name, counters...
   local name=$1; shift
   timeout -s KILL 300 rocprofv3 --pmc "$@" -d $OUT/prof_$name -o run --output-format csv -- python3 $R/bench.py $SHORT > $OUT/prof_$name.log 2>&1
