@@ -141,8 +141,15 @@ typedef int (*tvm_bbolt_visit)(void* ctx, const tvm_str* path, size_t depth, con
 int tvm_bbolt_walk(const void* bytes, size_t len, tvm_bbolt_visit visit, void* ctx, char* err, size_t errlen);
 /* Decode + flatten into device images. Must be called once, before tvm_engine_open. */
 int tvm_db_finalize(tvm_db* db, char* err, size_t errlen);
-/* Statistics: [0] platforms [1] keys [2] advisories [3] interval rows [4] key-arena bytes */
+/* Statistics: [0] platforms [1] keys [2] advisories [3] device row-array length (pad rows and
+ * duplicated class-0 rows included: tvm_db_layout_stats splits it up) [4] key-arena bytes */
 void tvm_db_stats(const tvm_db* db, uint64_t out[5]);
+/* The row layouts a finalized DB was flattened into: [0] device row-array length = [1] + [2] + [3]
+ * [1] pad rows (every key's run starts on a 128-byte line) [2] advisory interval rows (the sum
+ * of the keys' full lists, what tvm_db_rows_many reports per key) [3] duplicated class-0 rows
+ * (the lists A of the keys split by version class) [4] rows that carry their arch / CPE /
+ * ksplice predicates inline [5] keys split by version class */
+void tvm_db_layout_stats(const tvm_db* db, uint64_t out[6]);
 
 /* ---- device engine -------------------------------------------------------------------- */
 /* Uploads the finalized tables to HIP device `device`.  `db` must outlive the engine. */

@@ -59,6 +59,92 @@ def test_bulk_add_equals_per_target_adds(cfg):
     bulk.close()
 
 
+def _outputs(mb):
+    total, errp, bits = mb.run()
+    assert errp == -1 and bits == 0
+    pairs = mb.pairs()
+    vs = mb.vulns()
+    out = (pairs, mb.report(), vs.pkg.copy(), vs.rec.copy(), vs.walk(), vs.digest())
+    vs.close()
+    return out
+
+
+@pytest.mark.parametrize("order", ["attrs_first", "plain_first"])
+def test_bulk_add_appends_to_partial_group(order):
+    """Bulk adds into a batch that already holds packages, at sizes that are no multiple of the
+    64-package group: the partial group keeps its string offset, and the attribute column is
+    back-filled with the no-attribute word when the first attribute-carrying add comes after
+    plain ones (plain_first) - the batch equals the one built by add_many alone."""
+    from trivy_amd.batch import MatchBatch
+    sdb, eng = _engine(sm.C5_PLATS, 300, seed=61)
+    batch = sm.make_mix_batch(sdb, 3000, sm.C5_WEIGHTS, seed=62)
+    g = {sdb.plats[p][0]: (p, grp) for p, grp in batch.groups}
+    assert len(g) == len(sm.C5_PLATS)
+
+    def seg(bucket, lo=0, hi=None):
+        p, grp = g[bucket]
+        return p, lo, len(grp["key"]) if hi is None else hi
+
+    def cols_of(segs, per_target):
+        groups = [(p, {k: v[lo:hi] for k, v in g[sdb.plats[p][0]][1].items()}) for p, lo, hi in segs]
+        return sm.BulkCols(sdb, sm.MixBatch(groups), per_target=per_target)
+
+    def bulk_plain(mb, segs):  # tvm_batch_add_targets: no attribute columns at all
+        c = cols_of(segs, 90)
+        assert not c.flags.any()
+        return mb.add_targets(c.buckets, c.ends, c.arena, c.noff, c.nlen, c.voff, c.vlen)
+
+    def bulk_attrs(mb, segs, empty_first=False):
+        c = cols_of(segs, 70)
+        assert c.flags.any()
+        if not empty_first:
+            return c.add(mb)
+        sets = np.zeros(c.n, np.uint32)
+        inv = {v: k for k, v in c.combos.items()}
+        for ci in np.unique(c.combo[c.combo >= 0]).tolist():
+            sets[c.combo == ci] = mb.cpe_set(list(inv[ci][0]), inv[ci][1])
+        return mb.add_targets([c.buckets[0]] + c.buckets, np.concatenate([[0], c.ends]).astype(np.uint64), c.arena,
+                              c.noff, c.nlen, c.voff, c.vlen, flags=np.concatenate([c.flags[:1], c.flags]),
+                              arch_off=c.aoff, arch_len=c.alen, cpe_sets=sets)
+
+    def many(mb, segs):
+        for p, lo, hi in segs:
+            sm.add_slice(mb, sdb, p, g[sdb.plats[p][0]][1], lo, hi)
+
+    if order == "attrs_first":
+        steps = [(many, [seg("alma 8", 0, 37)]),
+                 (bulk_attrs, [seg("Red Hat"), seg("Oracle Linux 8")]),
+                 (many, [seg("alma 8", 37, 42)]),
+                 (bulk_plain, [seg("alma 8", 42), seg("alma 9"), seg("alpine 3.19")]),
+                 (lambda mb, s: bulk_attrs(mb, s, empty_first=True),
+                  [seg("rocky 8"), seg("Oracle Linux 9"), seg("alpine 3.20"), seg("rocky 9")])]
+    else:
+        steps = [(bulk_plain, [seg("alma 9")]),
+                 (many, [seg("alma 8", 0, 37)]),
+                 (bulk_attrs, [seg("Red Hat"), seg("rocky 8")]),
+                 (bulk_plain, [seg("alma 8", 37), seg("alpine 3.19")]),
+                 (many, [seg("Oracle Linux 8"), seg("alpine 3.20", 0, 5)]),
+                 (lambda mb, s: bulk_attrs(mb, s, empty_first=True),
+                  [seg("Oracle Linux 9"), seg("alpine 3.20", 5), seg("rocky 9")])]
+    one, mixed = MatchBatch(eng), MatchBatch(eng)
+    cuts, mid = [], 0
+    for fn, segs in steps:
+        many(one, segs)
+        begin = len(mixed)
+        fn(mixed, segs)
+        assert len(mixed) == len(one) == begin + sum(hi - lo for _, lo, hi in segs)
+        cuts.append(len(mixed))
+        mid += fn is not many and begin % 64 != 0 and len(mixed) % 64 != 0
+    assert len(one) == len(batch) and all(x % 64 for x in cuts) and mid >= 1
+    (p1, r1, vp1, vr1, w1, d1), (p2, r2, vp2, vr2, w2, d2) = _outputs(one), _outputs(mixed)
+    assert len(p1) > 1000 and np.array_equal(p1, p2)
+    assert r1 == r2
+    assert np.array_equal(vp1, vp2) and np.array_equal(vr1, vr2)
+    assert w1 == (len(vp1), d1) and w2 == (len(vp2), d2) and d1 == d2
+    one.close()
+    mixed.close()
+
+
 def test_bulk_add_refuses_bad_attributes():
     import ctypes
 

@@ -314,6 +314,8 @@ void tvm_db_stats(const tvm_db* db, uint64_t out[5]) {
   out[4] = db->db.key_words.size() * 8;
 }
 
+void tvm_db_layout_stats(const tvm_db* db, uint64_t out[6]) { db->db.layout_stats(out); }
+
 const char* tvm_db_advisory_vuln_id(const tvm_db* db, uint32_t adv) {
   return adv < db->db.advs.size() ? db->db.advs[adv].vuln_id.c_str() : nullptr;
 }

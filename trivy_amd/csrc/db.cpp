@@ -322,6 +322,26 @@ uint32_t DB::key_rows(uint32_t plat, std::string_view name) const {
   return 0;
 }
 
+void DB::layout_stats(uint64_t out[6]) const {
+  uint64_t full = 0, dup = 0, split = 0, inl = 0;
+  for (size_t i = 0; i < slot_hash.size(); i++) {
+    if (!slot_hash[i]) continue;
+    const SlotVal& v = slot_val[i];
+    full += slot_rows(v.name_len, v.row_begin, v.row_count, 1).y;
+    if (v.name_len & SLOT_CLS_SPLIT) {
+      dup += slot_rows(v.name_len, v.row_begin, v.row_count, 0).y;
+      split++;
+    }
+  }
+  for (const Row& r : rows) inl += (r.adv & ROW_INLINE) ? 1 : 0;
+  out[0] = rows.size();
+  out[1] = n_pad_rows;
+  out[2] = full;
+  out[3] = dup;
+  out[4] = inl;
+  out[5] = split;
+}
+
 std::vector<int64_t> DB::redhat_cpes(const std::vector<std::string_view>& repos,
                                      const std::vector<std::string_view>& nvrs) const {
   std::vector<int64_t> out;
@@ -761,7 +781,8 @@ bool DB::compile_rows(const Platform& P, const Advisory& a, uint32_t ai, std::ve
 // class and load no RowAux.  Measured on C3's PEP 440 keys: 10.6 rows on average, ~half of
 // them for other classes.
 void DB::split_by_class(const Platform& P, uint32_t rb, uint32_t& cnt) {
-  if (P.drv != DRV_LIBRARY || P.cmp == CMP_MAVEN || cnt == 0 || cnt >= 0x10000u) return;
+  // a key of kSplitMaxRows rows or more keeps its one list (its count would run into the mark)
+  if (P.drv != DRV_LIBRARY || P.cmp == CMP_MAVEN || cnt == 0 || cnt >= kSplitMaxRows) return;
   std::vector<uint32_t> a;
   for (uint32_t r = rb; r < rb + cnt; r++) {
     const bool filt = rows[r].adv & ROW_FILTER;
@@ -798,6 +819,7 @@ void DB::build_index() {
   row_off.clear();
   aux.clear();
   aux_ids.clear();
+  n_pad_rows = 0;
   std::vector<uint8_t> kb;
   std::vector<uint32_t> row_begin(keys.size()), row_count(keys.size());
   for (size_t k = 0; k < keys.size(); k++) {
@@ -812,6 +834,7 @@ void DB::build_index() {
       rows.push_back(pad);
       row_off.push_back(RowOff{});
       aux.push_back(RowAux{});
+      n_pad_rows++;
     }
     row_begin[k] = uint32_t(rows.size());
     for (uint32_t ai : key.advs) compile_rows(P, advs[ai], ai, kb);

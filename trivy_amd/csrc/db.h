@@ -92,6 +92,10 @@ class DB {
   // Interval rows of key (plat, name) in the device tables (0: no key) - the host pre-probe of
   // a package's work (multi-GPU shard balance, heavy-first tile order).
   uint32_t key_rows(uint32_t plat, std::string_view name) const;
+  // Which row layouts build_index produced: [0] rows.size(), [1] pad rows, [2] advisory interval
+  // rows (the sum of the keys' full lists), [3] duplicated class-0 rows (the sum of the split
+  // keys' lists A), [4] ROW_INLINE rows, [5] keys with SLOT_CLS_SPLIT.  [0] = [1] + [2] + [3].
+  void layout_stats(uint64_t out[6]) const;
 
   // Red Hat CPE resolution (trivy-db RedHatRepoToCPEs / RedHatNVRToCPEs): the unique CPE
   // indices of content sets + NVRs, in first-seen order.
@@ -117,6 +121,7 @@ class DB {
   std::vector<PlatInfo> plat_info;
   uint64_t slot_mask = 0;
   uint64_t n_rows_total = 0;
+  uint64_t n_pad_rows = 0;  // line-alignment rows between the keys' runs (never swept)
   bool has_filters = false;
 
   const Bucket& tree() const { return root_; }
@@ -133,6 +138,12 @@ class DB {
   void flatten_library(uint32_t plat, const std::vector<std::pair<const Bucket*, int32_t>>& roots);
   bool compile_rows(const Platform& P, const Advisory& a, uint32_t ai, std::vector<uint8_t>& kb);
   static constexpr uint32_t kRowSplit = 1u << 31;  // split_by_class's mark on a packed count
+  // A key is split only below this many rows: the packed count |A| | |B| << 16 (|A| < |B|) then
+  // stays below the mark, which build_index strips again
+  static constexpr uint32_t kSplitMaxRows = 0x8000;
+  static_assert(kSplitMaxRows - 1 <= 0xFFFFu, "|A| and |B| are 16-bit fields of a packed count");
+  static_assert((((kSplitMaxRows - 1) << 16) | (kSplitMaxRows - 1)) < kRowSplit,
+                "a packed count never reaches the split mark's bit");
   static constexpr uint32_t kRowsPerLine = 4;       // 32-B rows per 128-B line (a key's run starts on one)
   void split_by_class(const Platform& P, uint32_t row_begin, uint32_t& row_count);
   void build_index();

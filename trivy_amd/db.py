@@ -73,6 +73,17 @@ class DB:
         lib().tvm_db_stats(self.h, out)
         return dict(zip(["platforms", "keys", "advisories", "rows", "key_bytes"], list(out)))
 
+    def layout_stats(self):
+        """Which row layouts finalize() built (tvm_db_layout_stats): rows = pad_rows + interval_rows
+        + class0_dup_rows; inline_rows carry their predicates in the row (ROW_INLINE), split_keys
+        keep a class-0 list in front of their full list (SLOT_CLS_SPLIT)."""
+        if not self._finalized:
+            raise ValueError("layout_stats: the DB is not finalized")
+        out = (ctypes.c_uint64 * 6)()
+        lib().tvm_db_layout_stats(self.h, out)
+        return dict(zip(["rows", "pad_rows", "interval_rows", "class0_dup_rows", "inline_rows", "split_keys"],
+                        list(out)))
+
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         if h and _lib._lib is not None:
