@@ -150,6 +150,16 @@ void tvm_db_stats(const tvm_db* db, uint64_t out[5]);
  * (the lists A of the keys split by version class) [4] rows that carry their arch / CPE /
  * ksplice predicates inline [5] keys split by version class */
 void tvm_db_layout_stats(const tvm_db* db, uint64_t out[6]);
+/* The 16-byte hot rows of the dpkg grammar (a second row array, parallel to the 32-byte rows: the
+ * bytes of a bound behind its key's common prefix): [0..7] dpkg-grammar keys by prefix length
+ * [8] rows a hot row expresses [9] rows that fall back to the 32-byte row (pad rows in neither) */
+void tvm_db_row16_stats(const tvm_db* db, uint64_t out[10]);
+/* The hot-row compare on the host: `version` against every row of key (bucket, name), in row order.
+ * path[i]: 0 the hot row decided, 1 its window tied (the 32-byte row decided), 2 a fall-back row;
+ * result[i]: 1 the row matches.  Returns the key's row count (at most `cap` entries are written),
+ * -1 when the bucket or the key is absent. */
+int tvm_row16_eval_host(const tvm_db* db, const char* bucket, const char* name, size_t name_len, const char* version,
+                        size_t version_len, uint8_t* path, uint8_t* result, size_t cap);
 
 /* ---- device engine -------------------------------------------------------------------- */
 /* Uploads the finalized tables to HIP device `device`.  `db` must outlive the engine. */

@@ -134,6 +134,9 @@ _SIG = [
     ("tvm_db_finalize", ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_db_stats", None, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tvm_db_layout_stats", None, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    ("tvm_db_row16_stats", None, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    ("tvm_row16_eval_host", ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
+                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     ("tvm_engine_open", _P, [_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_engine_close", None, [_P]),
     ("tvm_engine_swap", ctypes.c_int, [_P, _P, ctypes.c_char_p, ctypes.c_size_t]),

@@ -315,6 +315,61 @@ void tvm_db_stats(const tvm_db* db, uint64_t out[5]) {
 }
 
 void tvm_db_layout_stats(const tvm_db* db, uint64_t out[6]) { db->db.layout_stats(out); }
+void tvm_db_row16_stats(const tvm_db* db, uint64_t out[10]) { db->db.row16_stats(out); }
+
+// The hot-row compare (common.h row16_*) of one installed version against every row of a key, on
+// the host: the code the hot-row sweep runs per pair, with the full-Row path restated on the
+// whole keys (key_cmp) for the pairs it leaves open.
+int tvm_row16_eval_host(const tvm_db* db, const char* bucket, const char* name, size_t name_len, const char* version,
+                        size_t version_len, uint8_t* path, uint8_t* result, size_t cap) {
+  if (!db || !db->finalized || !bucket || !name || !version) return -1;
+  const DB& d = db->db;
+  const int32_t plat = d.find_plat(bucket);
+  if (plat < 0) return -1;
+  uint64_t pfx = 0;
+  uint32_t rb = 0, cnt = 0;
+  if (!d.key_row16(uint32_t(plat), std::string_view(name, name_len), pfx, rb, cnt)) return -1;
+  std::vector<uint8_t> kb;
+  struct Sink {
+    std::vector<uint8_t>* v;
+    void put(uint8_t b) { v->push_back(b); }
+  } sink{&kb};
+  uint32_t cls = 0;
+  const bool valid = encode_version_cls(d.plats[size_t(plat)].cmp, reinterpret_cast<const uint8_t*>(version),
+                                        uint32_t(version_len), sink, cls);
+  if (!valid) kb.clear();
+  const uint32_t kl = uint32_t(kb.size());
+  std::vector<uint64_t> kw((kb.size() + 7) / 8 + 1, 0);  // memory-order words, zero padded (key_cmp)
+  for (size_t i = 0; i < kb.size(); i++) kw[i / 8] |= uint64_t(kb[i]) << (8 * (i % 8));
+  uint64_t k[3] = {0, 0, 0};  // the 24-byte big-endian head, as the probe keeps it
+  for (size_t i = 0; i < kb.size() && i < 24; i++) k[i / 8] |= uint64_t(kb[i]) << (8 * (7 - i % 8));
+  const uint32_t P = uint32_t(pfx) & 0xFFu;
+  uint64_t ph;
+  uint32_t pt;
+  row16_pkg(k[0], k[1], k[2], kl, P, row16_prefix_cmp(k[0], kl, pfx), valid, ph, pt);
+  for (uint32_t i = 0; i < cnt && i < cap; i++) {
+    const Row16& h = d.rows16[rb + i];
+    bool slow = false;
+    bool m = row16_test(ph, pt, h, slow);
+    if (slow) {
+      const Row& r = d.rows[rb + i];
+      const RowOff& o = d.row_off[rb + i];
+      m = true;
+      if (!(r.hi_len & KEY_INF)) {
+        const int c = key_cmp(kw.data(), kl, d.key_words.data() + o.hi_off, r.hi_len & KEY_LEN_MASK);
+        m = (r.hi_len & KEY_INCL) ? c <= 0 : c < 0;
+      }
+      if (m && !(r.lo_len & KEY_INF)) {
+        const int c = key_cmp(kw.data(), kl, d.key_words.data() + o.lo_off, r.lo_len & KEY_LEN_MASK);
+        m = (r.lo_len & KEY_INCL) ? c >= 0 : c > 0;
+      }
+      m = (m && valid) || (r.adv & ROW_ALWAYS);
+    }
+    if (path) path[i] = (h.tail & 0xFFu) == R16_FALLBACK ? 2 : slow ? 1 : 0;
+    if (result) result[i] = m ? 1 : 0;
+  }
+  return int(cnt);
+}
 
 const char* tvm_db_advisory_vuln_id(const tvm_db* db, uint32_t adv) {
   return adv < db->db.advs.size() ? db->db.advs[adv].vuln_id.c_str() : nullptr;

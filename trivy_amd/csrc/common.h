@@ -154,8 +154,9 @@ TVM_HD uint2 slot_rows(uint32_t name_len, uint32_t row_begin, uint32_t row_count
 // Device hash slot: one 64-B cache line holding the hash, the row range and the first
 // kSlotNameWords*8 bytes of the name (memory order, zero padded), so a probe verifies the
 // name from the same line it read the hash from; longer names finish against the name
-// arena from byte 40 on.  (The host keeps slot_hash/slot_val for its own lookups.)
-constexpr uint32_t kSlotNameWords = 5;
+// arena from byte 32 on.  (The host keeps slot_hash/slot_val for its own lookups.)
+// pfx: a dpkg-grammar key's common bound prefix (row16_* below), 0 for every other key.
+constexpr uint32_t kSlotNameWords = 4;
 struct alignas(64) Slot {
   uint64_t hash;       // 0 = empty
   uint32_t row_begin;
@@ -163,6 +164,7 @@ struct alignas(64) Slot {
   uint32_t name_len;   // bytes | SLOT_POISONED
   uint32_t name_off;   // full name in the name arena
   uint64_t name[kSlotNameWords];
+  uint64_t pfx;        // low byte P (0..7); the P prefix bytes big-endian from bit 63 down, zero padded
 };
 static_assert(sizeof(Slot) == 64, "one cache line per slot");
 // Slot fingerprints (DB::slot_fp): one byte a slot, 0 = empty, else the hash's top byte (1 for
@@ -272,6 +274,72 @@ TVM_HD int key_cmp_pre2(uint64_t a0, uint64_t a1, const uint64_t* a_full, uint32
 TVM_HD int key_cmp_pre(const uint64_t* a, uint32_t na, uint64_t b0, uint64_t b1, const uint64_t* b_full,
                        uint32_t nb) {
   return key_cmp_pre2(a[0], a[1], a, na, b0, b1, b_full, nb);
+}
+
+// ---- 16-byte prefix-stripped dpkg rows (DB::rows16, parallel to DB::rows) -------------------
+// A dpkg-grammar row has no lower bound and no flags, and the sort keys of one package's fixed
+// versions share their first bytes (epoch, the leading upstream numbers).  The key's slot holds
+// that common prefix (P <= kPfxCap bytes, Slot::pfx) and a hot row only the kRow16Window bytes
+// after it, so the sweep reads 16 bytes a pair instead of 32.  The probe compares the installed
+// key with the prefix once per package (below / above: every bounded row of the key is decided;
+// equal: the windows are compared per row).  A hot row decides its pair unless both windows are
+// equal and both keys run past the window, or its code is R16_FALLBACK (a row it cannot express):
+// those pairs take the full Row (24-byte head, then the key arena) as before.
+constexpr uint32_t kPfxCap = 7;
+constexpr uint32_t kRow16Window = 11;
+struct alignas(16) Row16 {
+  uint32_t adv;   // as Row::adv: the advisory index | ROW_ALWAYS
+  uint32_t tail;  // window bytes 8..10 big-endian in bits 31..8; low byte: the code
+  uint64_t head;  // window bytes 0..7 big-endian (the bound's key bytes P .. P+7), zero padded
+};
+static_assert(sizeof(Row16) == 16, "one 16-byte load per pair");
+// Row16 code byte: the bound's length past the prefix, clamped to kRow16Window + 1 ("runs past the
+// window"); R16_INF: no upper bound (an unfixed advisory); R16_FALLBACK: read the full Row.
+enum : uint32_t { R16_LEN_MASK = 0x0F, R16_INF = 0x80, R16_FALLBACK = 0xFF };
+// The package's side of the compare (per package, built once: row16_pkg): head / tail as Row16,
+// the tail's low byte = its key length past the prefix (clamped alike) | the prefix outcome |
+// R16_PKG_VALID (the installed version parsed).
+enum : uint32_t { R16_PFX_EQ = 0, R16_PFX_BELOW = 1, R16_PFX_ABOVE = 2, R16_PFX_SHIFT = 4, R16_PKG_VALID = 0x40 };
+
+// The installed key (k0: its first 8 bytes big-endian, zero padded; kl: its length) against a
+// slot's prefix: R16_PFX_BELOW / ABOVE when it sorts before / after every key that starts with
+// the prefix, else R16_PFX_EQ.  A key shorter than P that is a prefix of the prefix is below.
+TVM_HD uint32_t row16_prefix_cmp(uint64_t k0, uint32_t kl, uint64_t pfx) {
+  const uint32_t P = uint32_t(pfx) & 0xFFu;
+  const uint64_t mask = P ? ~0ull << (64 - 8 * P) : 0ull;
+  const uint64_t a = k0 & mask, b = pfx & mask;
+  if (a != b) return a < b ? R16_PFX_BELOW : R16_PFX_ABOVE;
+  return kl < P ? R16_PFX_BELOW : R16_PFX_EQ;
+}
+// Key bytes [P, P + kRow16Window) of a key given by its 24-byte big-endian head (zero padded) and
+// its length: head = the first 8 of them, tail = the last 3 in bits 31..8 | the clamped length.
+TVM_HD void row16_window(uint64_t k0, uint64_t k1, uint64_t k2, uint32_t kl, uint32_t P, uint64_t& head, uint32_t& tail) {
+  const uint32_t sh = 8 * P;
+  head = P ? (k0 << sh) | (k1 >> (64 - sh)) : k0;
+  const uint64_t w1 = P ? (k1 << sh) | (k2 >> (64 - sh)) : k1;
+  const uint32_t n = kl > P ? kl - P : 0u;
+  tail = (uint32_t(w1 >> 32) & 0xFFFFFF00u) | (n > kRow16Window ? kRow16Window + 1 : n);
+}
+TVM_HD void row16_pkg(uint64_t k0, uint64_t k1, uint64_t k2, uint32_t kl, uint32_t P, uint32_t outcome, bool valid,
+                      uint64_t& head, uint32_t& tail) {
+  row16_window(k0, k1, k2, kl, P, head, tail);
+  tail |= (outcome << R16_PFX_SHIFT) | (valid ? R16_PKG_VALID : 0u);
+}
+// The interval test of one pair on the hot row, branch-free (as cmp_head): the result holds
+// unless `slow` is set - then the caller evaluates the full Row.
+TVM_HD bool row16_test(uint64_t ph, uint32_t pt, const Row16& r, bool& slow) {
+  const uint32_t code = r.tail & 0xFFu;
+  const uint32_t a1 = pt & 0xFFFFFF00u, b1 = r.tail & 0xFFFFFF00u;
+  const bool eq0 = ph == r.head, eq = eq0 && a1 == b1;
+  const bool lt = ph < r.head || (eq0 && a1 < b1);
+  const uint32_t na = pt & R16_LEN_MASK, nb = code & R16_LEN_MASK;
+  const uint32_t out = (pt >> R16_PFX_SHIFT) & 3u;
+  const bool inf = (code & R16_INF) != 0;
+  const bool tie = out == R16_PFX_EQ && eq && na > kRow16Window && nb > kRow16Window;
+  slow = code == R16_FALLBACK || (tie && !inf);
+  const bool below = out == R16_PFX_BELOW || (out == R16_PFX_EQ && (eq ? na < nb : lt));
+  const bool m = (inf || below) && (pt & R16_PKG_VALID);
+  return m || (r.adv & ROW_ALWAYS);
 }
 
 }  // namespace tvm

@@ -322,6 +322,26 @@ uint32_t DB::key_rows(uint32_t plat, std::string_view name) const {
   return 0;
 }
 
+void DB::row16_stats(uint64_t out[10]) const {
+  for (int i = 0; i < 10; i++) out[i] = row16_stats_[i];
+}
+
+bool DB::key_row16(uint32_t plat, std::string_view name, uint64_t& pfx, uint32_t& row_begin, uint32_t& row_count) const {
+  if (slot_hash.empty()) return false;
+  const uint64_t h = pkg_key_hash(plat, reinterpret_cast<const uint8_t*>(name.data()), uint32_t(name.size()));
+  for (uint64_t i = h & slot_mask; slot_hash[i]; i = (i + 1) & slot_mask) {
+    if (slot_hash[i] != h) continue;
+    const Key& k = keys[slot_key[i]];
+    if (k.plat != plat || k.name != name) continue;
+    const uint2 full = slot_rows(slot_val[i].name_len, slot_val[i].row_begin, slot_val[i].row_count, 1);
+    pfx = slots[i].pfx;
+    row_begin = full.x;
+    row_count = full.y;
+    return true;
+  }
+  return false;
+}
+
 void DB::layout_stats(uint64_t out[6]) const {
   uint64_t full = 0, dup = 0, split = 0, inl = 0;
   for (size_t i = 0; i < slot_hash.size(); i++) {
@@ -813,6 +833,45 @@ void DB::split_by_class(const Platform& P, uint32_t rb, uint32_t& cnt) {
   cnt = uint32_t(a.size()) | (cnt << 16) | kRowSplit;
 }
 
+// The hot rows (common.h Row16) of one dpkg-grammar key's run [rb, rb + cnt) and the key's prefix
+// word (Slot::pfx): P = the longest common prefix of the keys of the rows a Row16 can express with
+// a bound (no lower bound, an exclusive upper bound, no flag but ROW_ALWAYS), capped at kPfxCap.
+uint64_t DB::row16_build(uint32_t rb, uint32_t cnt) {
+  auto plain = [](const Row& r) {
+    return (r.lo_len & KEY_INF) && !(r.adv & ~(ROW_ADV_MASK | ROW_ALWAYS)) && !(r.hi_len & KEY_INCL);
+  };
+  uint32_t P = kPfxCap;
+  uint64_t first = 0;
+  bool any = false;
+  for (uint32_t i = rb; i < rb + cnt; i++) {
+    const Row& r = rows[i];
+    if (!plain(r) || (r.hi_len & KEY_INF)) continue;
+    const uint32_t nh = r.hi_len & KEY_LEN_MASK;
+    if (!any) first = r.hi_pre0;
+    any = true;
+    P = std::min(P, nh);
+    const uint64_t d = first ^ r.hi_pre0;
+    if (d) P = std::min<uint32_t>(P, uint32_t(__builtin_clzll(d)) / 8);
+  }
+  if (!any) P = 0;
+  for (uint32_t i = rb; i < rb + cnt; i++) {
+    const Row& r = rows[i];
+    Row16 h{};
+    h.adv = r.adv;
+    if (!plain(r)) {
+      h.tail = R16_FALLBACK;
+      row16_stats_[9]++;
+    } else {
+      if (r.hi_len & KEY_INF) h.tail = R16_INF;
+      else row16_window(r.hi_pre0, r.hi_pre1, r.hi_pre2, r.hi_len & KEY_LEN_MASK, P, h.head, h.tail);
+      row16_stats_[8]++;
+    }
+    rows16[i] = h;
+  }
+  row16_stats_[P]++;
+  return P ? (first & (~0ull << (64 - 8 * P))) | P : 0ull;
+}
+
 void DB::build_index() {
   // rows + key arena
   rows.clear();
@@ -828,7 +887,8 @@ void DB::build_index() {
     // every key's rows start on a 128-byte line (4 rows): an L2 miss fetches whole 128-B lines
     // (profiles/r06/calib.txt), so a run of n rows costs ceil(n / 4) lines instead of up to one
     // more; the pad rows between runs are never swept
-    while (rows.size() % kRowsPerLine) {
+    // (a dpkg-grammar key on two lines of 32-B rows: one 128-B line of its 16-B hot rows, rows16)
+    while (rows.size() % (P.cmp == CMP_DEB ? kRows16PerLine : kRowsPerLine)) {
       Row pad{};
       pad.lo_len = pad.hi_len = KEY_INF;
       rows.push_back(pad);
@@ -842,6 +902,17 @@ void DB::build_index() {
     split_by_class(P, row_begin[k], row_count[k]);
   }
   n_rows_total = rows.size();
+  // hot rows: R16_FALLBACK wherever no dpkg key's run is (other grammars, pad rows)
+  Row16 fb{};
+  fb.tail = R16_FALLBACK;
+  rows16.assign(rows.size(), fb);
+  for (uint64_t& x : row16_stats_) x = 0;
+  std::vector<uint64_t> key_pfx(keys.size(), 0);
+  for (size_t k = 0; k < keys.size(); k++) {
+    if (plats[keys[k].plat].cmp == CMP_DEB) key_pfx[k] = row16_build(row_begin[k], row_count[k]);
+    else  // the key's full list (a split key's packed count: |A| | |B| << 16)
+      row16_stats_[9] += (row_count[k] & kRowSplit) ? (row_count[k] & ~kRowSplit) >> 16 : row_count[k];
+  }
   if (key_words.empty()) key_words.push_back(0);
   if (aux_ids.empty()) aux_ids.push_back(0);
   // CPE indices present only in the repository / nvr maps widen the bitset too
@@ -900,6 +971,7 @@ void DB::build_index() {
     sl.row_count = v.row_count;
     sl.name_len = v.name_len;
     sl.name_off = v.name_off;
+    sl.pfx = key_pfx[k];
     for (size_t b = 0; b < key.name.size() && b < 8 * kSlotNameWords; b++)
       sl.name[b / 8] |= uint64_t(uint8_t(key.name[b])) << (8 * (b % 8));
     name_arena.insert(name_arena.end(), key.name.begin(), key.name.end());

@@ -96,6 +96,11 @@ class DB {
   // rows (the sum of the keys' full lists), [3] duplicated class-0 rows (the sum of the split
   // keys' lists A), [4] ROW_INLINE rows, [5] keys with SLOT_CLS_SPLIT.  [0] = [1] + [2] + [3].
   void layout_stats(uint64_t out[6]) const;
+  // The hot-row layout (rows16): [0..7] dpkg-grammar keys by prefix length P, [8] hot rows (the
+  // rows a Row16 expresses), [9] R16_FALLBACK rows; pad rows are in neither.
+  void row16_stats(uint64_t out[10]) const;
+  // The prefix word (Slot::pfx) of key (plat, name) and its row range; false: no such key.
+  bool key_row16(uint32_t plat, std::string_view name, uint64_t& pfx, uint32_t& row_begin, uint32_t& row_count) const;
 
   // Red Hat CPE resolution (trivy-db RedHatRepoToCPEs / RedHatNVRToCPEs): the unique CPE
   // indices of content sets + NVRs, in first-seen order.
@@ -115,6 +120,8 @@ class DB {
   std::vector<uint8_t> name_arena;
   std::vector<Row> rows;
   std::vector<RowOff> row_off;  // parallel to rows (the dpkg grammar's rows keep their offsets here only)
+  std::vector<Row16> rows16;    // parallel to rows: the dpkg grammar's 16-byte hot rows (common.h row16_*);
+                                // R16_FALLBACK for every other row
   std::vector<RowAux> aux;          // parallel to rows (read only for ROW_FILTER rows)
   std::vector<uint32_t> aux_ids;
   std::vector<uint64_t> key_words;
@@ -145,6 +152,9 @@ class DB {
   static_assert((((kSplitMaxRows - 1) << 16) | (kSplitMaxRows - 1)) < kRowSplit,
                 "a packed count never reaches the split mark's bit");
   static constexpr uint32_t kRowsPerLine = 4;       // 32-B rows per 128-B line (a key's run starts on one)
+  static constexpr uint32_t kRows16PerLine = 8;     // 16-B hot rows per line: a dpkg key's run starts on one
+  uint64_t row16_stats_[10] = {};
+  uint64_t row16_build(uint32_t row_begin, uint32_t row_count);
   void split_by_class(const Platform& P, uint32_t row_begin, uint32_t& row_count);
   void build_index();
 };

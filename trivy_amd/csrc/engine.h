@@ -29,6 +29,7 @@ struct DevDB {
   const uint8_t* name_arena = nullptr;
   const Row* rows = nullptr;
   const RowOff* row_off = nullptr;  // parallel to rows
+  const Row16* rows16 = nullptr;    // parallel to rows: the dpkg grammar's hot rows (common.h)
   const uint64_t* key_words = nullptr;
   const PlatInfo* plats = nullptr;
   uint32_t n_plats = 0;

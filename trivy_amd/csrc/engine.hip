@@ -176,7 +176,7 @@ Engine* Engine::open(const DB& db, int device, std::string& err) {
     delete e;
     return nullptr;
   }
-  Slot* sl; uint8_t* fp; uint8_t* na; Row* rows; RowOff* ro; uint64_t* kw; PlatInfo* pl; RowAux* ax; uint32_t* ai;
+  Slot* sl; uint8_t* fp; uint8_t* na; Row* rows; RowOff* ro; Row16* r16; uint64_t* kw; PlatInfo* pl; RowAux* ax; uint32_t* ai;
   bool ok = upload_vec(db.aux, &ax, e->allocs_, e->table_bytes_, err) &&
             upload_vec(db.aux_ids, &ai, e->allocs_, e->table_bytes_, err) &&
             upload_vec(db.slots, &sl, e->allocs_, e->table_bytes_, err) &&
@@ -184,6 +184,7 @@ Engine* Engine::open(const DB& db, int device, std::string& err) {
             upload_vec(db.name_arena, &na, e->allocs_, e->table_bytes_, err) &&
             upload_vec(db.rows, &rows, e->allocs_, e->table_bytes_, err) &&
             upload_vec(db.row_off, &ro, e->allocs_, e->table_bytes_, err) &&
+            upload_vec(db.rows16, &r16, e->allocs_, e->table_bytes_, err) &&
             upload_vec(db.key_words, &kw, e->allocs_, e->table_bytes_, err) &&
             upload_vec(db.plat_info, &pl, e->allocs_, e->table_bytes_, err);
   if (!ok) {
@@ -196,6 +197,7 @@ Engine* Engine::open(const DB& db, int device, std::string& err) {
   e->d_.name_arena = na;
   e->d_.rows = rows;
   e->d_.row_off = ro;
+  e->d_.rows16 = r16;
   e->d_.key_words = kw;
   e->d_.plats = pl;
   e->d_.aux = ax;
@@ -891,6 +893,7 @@ bool Engine::verify(std::string& err) {
          check(d_.name_arena, db.name_arena.data(), db.name_arena.size(), "name_arena") &&
          check(d_.rows, db.rows.data(), db.rows.size() * sizeof(Row), "rows") &&
          check(d_.row_off, db.row_off.data(), db.row_off.size() * sizeof(RowOff), "row_off") &&
+         check(d_.rows16, db.rows16.data(), db.rows16.size() * sizeof(Row16), "rows16") &&
          check(d_.key_words, db.key_words.data(), db.key_words.size() * 8, "key_words") &&
          check(d_.plats, db.plat_info.data(), db.plat_info.size() * sizeof(PlatInfo), "plats") &&
          check(d_.aux, db.aux.data(), db.aux.size() * sizeof(RowAux), "aux") &&

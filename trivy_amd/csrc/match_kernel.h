@@ -15,7 +15,7 @@
 //        bytes stay in registers (big-endian, ready for two u64 compares), bytes 16..31 go
 //        to a per-package tail slot, longer keys to the spill area;
 //     2. the name is read as words (aligned LDS dwords + v_alignbyte), hashed word by word
-//        and probed in the open-addressing index (one 64-B slot = hash, rows, first 40 name
+//        and probed in the open-addressing index (one 64-B slot = hash, rows, first 32 name
 //        bytes), so a probe is one memory round trip;
 //     3. out: per package {k0, k1} and {row_begin, row_count, key info, spill offset}.
 //   sweep_kernel
@@ -101,8 +101,11 @@ namespace {
 
 // KI_MVN: a Maven package whose key has program rows (the sweep defers those pairs)
 // KI_H24: a dpkg-grammar package (its rows carry 24-byte key heads, Row::hi_pre2)
+// KI_P / KI_PFX (dpkg-only kernels): the key's prefix length P and the installed key's outcome
+// against the prefix (common.h row16_prefix_cmp), for the hot-row sweep
 enum : uint32_t { KI_VALID = 1u << 31, KI_SPILL = 1u << 30, KI_MVN = 1u << 29, KI_H24 = 1u << 25, KI_LEN = 0x3FFFu,
-                  KI_CLS_SHIFT = 26, KI_CLS_MASK = 7u };
+                  KI_CLS_SHIFT = 26, KI_CLS_MASK = 7u, KI_P_SHIFT = 14, KI_P_MASK = 7u, KI_PFX_SHIFT = 17,
+                  KI_PFX_MASK = 3u };
 
 // Block-wide exclusive scan of v over T lanes (wave shuffles + one LDS exchange); returns
 // the block total.  `wsum` holds T/64 words; two barriers.
@@ -188,19 +191,18 @@ __device__ __forceinline__ uint64_t name_hash(uint32_t plat, const uint8_t* s, u
   return key_hash_fin(h);
 }
 
-// Name check against a slot (first 40 bytes inline, loaded with the hash; the name's words
-// are re-read, which is cheaper than keeping five words live across the probe); longer
+// Name check against a slot (first 32 bytes inline, loaded with the hash; the name's words
+// are re-read, which is cheaper than keeping four words live across the probe); longer
 // names finish bytewise against the name arena.
 template <class P>
 __device__ __forceinline__ bool name_eq_slot(const uint8_t* s, uint32_t n, const uint4 q1, const uint4 q2,
                                              const uint4 q3, const uint8_t* arena) {
-  static_assert(kSlotNameWords == 5, "five inline name words");
+  static_assert(kSlotNameWords == 4, "four inline name words (q3.z / q3.w: Slot::pfx)");
   const uintptr_t a = reinterpret_cast<uintptr_t>(s);
   const P* base = reinterpret_cast<const P*>(a & ~uintptr_t(3));
   const uint32_t sh = uint32_t(a & 3);
   const uint64_t y[kSlotNameWords] = {q1.z | (uint64_t(q1.w) << 32), q2.x | (uint64_t(q2.y) << 32),
-                                      q2.z | (uint64_t(q2.w) << 32), q3.x | (uint64_t(q3.y) << 32),
-                                      q3.z | (uint64_t(q3.w) << 32)};
+                                      q2.z | (uint64_t(q2.w) << 32), q3.x | (uint64_t(q3.y) << 32)};
   bool eq = true;
 #pragma unroll
   for (uint32_t i = 0; i < kSlotNameWords; i++) eq &= (8 * i < n ? name_word(base, sh, i, n) : 0ull) == y[i];
@@ -220,7 +222,7 @@ __device__ __forceinline__ void probe_lookup(const ProbeArgs& a, uint32_t p, uin
                                             uint32_t nlen, const uint8_t* name, bool valid, uint64_t h,
                                             uint64_t start, bool found, uint4 q0, uint4 q0n, bool has_q0n,
                                             uint32_t& rbeg, uint32_t& cnt, uint32_t* sflags = nullptr,
-                                            uint32_t cls = 0);
+                                            uint32_t cls = 0, uint64_t* pfx = nullptr);
 
 __device__ __forceinline__ uint4 slot_head(const ProbeArgs& a, uint64_t i) {
   return reinterpret_cast<const uint4*>(a.db.slots + (i & a.db.slot_mask))[0];
@@ -299,8 +301,11 @@ __device__ __forceinline__ void probe_one(const ProbeArgs& a, uint32_t p, uint32
       }
       uint32_t cnt = 0, rbeg = 0;
       if constexpr (!kPre) heads();
+      uint64_t pfx = 0;
       if (!(DIAG & 2)) probe_lookup<P>(a, p, plat, pi, nlen, name, (kinfo & KI_VALID) != 0, h, start, found, q0, q0n, has_q0n,
-                                          rbeg, cnt);
+                                          rbeg, cnt, nullptr, 0, GM == GM_DEB ? &pfx : nullptr);
+      if constexpr (GM == GM_DEB)
+        kinfo |= ((uint32_t(pfx) & KI_P_MASK) << KI_P_SHIFT) | (row16_prefix_cmp(r.k0, kl, pfx) << KI_PFX_SHIFT);
       r.meta = make_uint4(rbeg, cnt, kinfo, koff);
       return;
     }
@@ -337,8 +342,9 @@ __device__ __forceinline__ void probe_one(const ProbeArgs& a, uint32_t p, uint32
   }
   uint32_t cnt = 0, rbeg = 0, sflags = 0;
   if constexpr (!kPre) heads();
+  uint64_t pfx = 0;
   if (!(DIAG & 2)) probe_lookup<P>(a, p, plat, pi, nlen, name, valid, h, start, found, q0, q0n, has_q0n, rbeg, cnt,
-                                   &sflags, cls);
+                                   &sflags, cls, GM == GM_DEB ? &pfx : nullptr);
   if (((GM >> CMP_MAVEN) & 1u) && pi.cmp == CMP_MAVEN) {
     // Maven rows compare parses, not keys (AUX_MVN): the installed version's parse, packed
     // into the batch scratch, and its text location take the tail slot - only when the key
@@ -371,6 +377,8 @@ __device__ __forceinline__ void probe_one(const ProbeArgs& a, uint32_t p, uint32
   r.k0 = valid && kl ? be_word(hs.w0, kl < 8 ? kl : 8) : 0ull;
   r.k1 = valid && kl > 8 ? be_word(hs.w1, kl < 16 ? kl - 8 : 8) : 0ull;
   r.k2 = valid && kl > 16 ? be_word(hs.w2, kl < 24 ? kl - 16 : 8) : 0ull;
+  if constexpr (GM == GM_DEB)
+    kinfo |= ((uint32_t(pfx) & KI_P_MASK) << KI_P_SHIFT) | (row16_prefix_cmp(r.k0, kl, pfx) << KI_PFX_SHIFT);
   r.meta = make_uint4(rbeg, cnt, kinfo, koff);
 }
 
@@ -378,7 +386,7 @@ template <class P>
 __device__ __forceinline__ void probe_lookup(const ProbeArgs& a, uint32_t p, uint32_t plat, const PlatInfo& pi,
                                             uint32_t nlen, const uint8_t* name, bool valid, uint64_t h,
                                             uint64_t start, bool found, uint4 q0, uint4 q0n, bool has_q0n,
-                                            uint32_t& rbeg, uint32_t& cnt, uint32_t* sflags, uint32_t cls) {
+                                            uint32_t& rbeg, uint32_t& cnt, uint32_t* sflags, uint32_t cls, uint64_t* pfx) {
   // parse-first drivers (debian.go:66-70) skip an unparsable package before the lookup;
   // lookup-first drivers (ubuntu.go:86-92) probe first, so a poisoned key still raises
   if (found && (valid || (pi.flags & PLAT_LOOKUP_FIRST))) {
@@ -399,6 +407,7 @@ __device__ __forceinline__ void probe_lookup(const ProbeArgs& a, uint32_t p, uin
         rbeg = rr.x;
         cnt = rr.y;
         if (sflags) *sflags = q1.x & (SLOT_MVN_C0 | SLOT_MVN_C1);
+        if (pfx) *pfx = q3.z | (uint64_t(q3.w) << 32);
       }
       break;
     }
@@ -819,16 +828,30 @@ __device__ __forceinline__ uint32_t sweep(const SweepArgs& a, SweepShared<FILT>&
 // LDS buffer, so no round waits on the other waves (the shared form needs a workgroup
 // barrier per round to place matches across waves); the waves' counts are combined once,
 // after the sweep.  DIRECT: the wave's re-sweep straight to the output (base = its offset).
-template <int K, int MBW, int FILT, bool DIRECT>
+// R16 = 3: the hot-row sweep of a dpkg-only batch - a pair loads its 16-byte Row16 (DB::rows16) and
+// tests it against the package's window (hot: Hot16, filled by sweep_tile); only a pair the hot
+// row leaves open (common.h row16_test: a window tie with both keys longer, R16_FALLBACK) reads
+// its 32-byte Row, as every pair does at R16 = 0.
+// R16 = 1 / 2 (measurement only, TVM_DIAG variants "diag_row16*", wrong match lists by
+// construction): a pair loads 16 bytes, not its Row - 1: rows[] read as a 16-byte array at the
+// pair's row index, 2: the first half of the pair's Row.  The bound is read as a 16-byte head of a
+// key no longer than its head, so no pair leaves the branch-free path or reads the key arena.
+struct Hot16 {
+  uint64_t* head;  // per tile package: common.h row16_pkg
+  uint32_t* tail;
+};
+template <int K, int MBW, int FILT, bool DIRECT, int R16 = 0>
 __device__ __forceinline__ uint32_t sweep_seg(const SweepArgs& a, const SweepShared<FILT>& s, uint32_t* madv,
                                               uint8_t* mq, const uint8_t* map, uint32_t nnz, uint32_t total,
-                                              uint32_t s0, uint32_t s1, uint32_t lane, unsigned long long base) {
+                                              uint32_t s0, uint32_t s1, uint32_t lane, unsigned long long base,
+                                              const Hot16& hot) {
   const unsigned long long lt = (1ull << lane) - 1ull;
   const uint32_t pbase = s.tile * kTile;
   const uint32_t shift = map_shift(total);
   uint32_t nm = 0;
   for (uint32_t b0 = s0; b0 < s1; b0 += 64 * K) {
-    Row row[K];
+    Row row[R16 == 3 ? 1 : K];
+    Row16 hrow[R16 == 3 ? K : 1];
     uint32_t qq[K], rid[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
@@ -842,14 +865,40 @@ __device__ __forceinline__ uint32_t sweep_seg(const SweepArgs& a, const SweepSha
       rid[k] = min(b0 + k * 64 + lane, s1 - 1) + s.nz_rd[r];
     }
 #pragma unroll
-    for (int k = 0; k < K; k++) row[k] = a.db.rows[rid[k]];
+    for (int k = 0; k < K; k++) {
+      if constexpr (R16 == 3) {
+        hrow[k] = a.db.rows16[rid[k]];
+      } else if constexpr (R16 != 0) {
+        const uint4 h = reinterpret_cast<const uint4*>(a.db.rows)[R16 == 1 ? rid[k] : 2 * rid[k]];
+        row[k].hi_pre0 = h.x | (uint64_t(h.y) << 32);
+        row[k].hi_pre1 = h.z | (uint64_t(h.w) << 32);
+        row[k].hi_pre2 = 0;
+        row[k].adv = h.w & ROW_ADV_MASK;
+        row[k].lo_len = KEY_INF;
+        row[k].hi_len = uint16_t(8u + (h.z & 15u));
+      } else {
+        row[k] = a.db.rows[rid[k]];
+      }
+    }
 #pragma unroll
     for (int k = 0; k < K; k++) {
-      const bool m = eval_row<FILT>(a, s, qq[k], pbase + qq[k], row[k], rid[k]) != 0 && b0 + k * 64 + lane < s1;
+      bool m;
+      if constexpr (R16 == 3) {
+        bool slow;
+        m = row16_test(hot.head[qq[k]], hot.tail[qq[k]], hrow[k], slow);
+#ifdef TVM_EXP_R16_NOTIE  // measurement only (make exp): an open pair is a miss and reads no Row - wrong lists by design
+        if (slow) m = false;
+#else
+        if (slow) m = eval_row<FILT>(a, s, qq[k], pbase + qq[k], a.db.rows[rid[k]], rid[k]) != 0;  // rare
+#endif
+      } else {
+        m = eval_row<FILT>(a, s, qq[k], pbase + qq[k], row[k], rid[k]) != 0;
+      }
+      m = m && b0 + k * 64 + lane < s1;
       const unsigned long long bal = __ballot(m);
       if (m) {
         const uint32_t pos = nm + uint32_t(__popcll(bal & lt));
-        const uint32_t adv = row[k].adv & ROW_ADV_MASK;
+        const uint32_t adv = (R16 == 3 ? hrow[k].adv : row[R16 == 3 ? 0 : k].adv) & ROW_ADV_MASK;
         if (DIRECT) {
           if (base + pos < a.out_cap) {
             a.out_pkg[base + pos] = a.out_base + a.p0 + pbase + qq[k];
@@ -870,7 +919,8 @@ __device__ __forceinline__ uint32_t sweep_seg(const SweepArgs& a, const SweepSha
 template <int K, int MB, int FILT, int SEG = 0>
 __device__ __forceinline__ void sweep_tile(const SweepArgs& a, SweepShared<FILT>& s, uint32_t* madv, uint8_t* mq,
                                            uint8_t* map, uint32_t t, uint32_t tid, const PkgRec& r,
-                                           const DeferQ& dq = DeferQ{nullptr, nullptr, 0}) {
+                                           const DeferQ& dq = DeferQ{nullptr, nullptr, 0},
+                                           const Hot16& hot = Hot16{nullptr, nullptr}) {
   const uint32_t lane = tid & 63, wave = tid >> 6;
   if (tid == 0) s.tile = t;
   const uint32_t p = t * kTile + tid;
@@ -879,6 +929,15 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, SweepShared<FILT>
   if constexpr (FILT < 2) s.k2[tid] = r.k2;
   s.kinfo[tid] = r.meta.z;
   s.koff[tid] = r.meta.w;
+  if constexpr (((SEG >> 2) & 3) == 3) {  // hot-row sweep: the package's window behind its key's prefix
+    const uint32_t ki = r.meta.z;
+    uint64_t hh;
+    uint32_t ht;
+    row16_pkg(r.k0, r.k1, r.k2, ki & KI_LEN, (ki >> KI_P_SHIFT) & KI_P_MASK, (ki >> KI_PFX_SHIFT) & KI_PFX_MASK,
+              (ki & KI_VALID) != 0, hh, ht);
+    hot.head[tid] = hh;
+    hot.tail[tid] = ht;
+  }
   if constexpr (FILT) s.pattr[tid] = (a.attr && p < a.n) ? a.attr[p] : make_uint2(PA_ARCH_NONE, 0xFFFFFFFFu);
   // compact the packages that have rows (ballot) and scan their row counts
   const uint32_t cnt = r.meta.y;
@@ -918,11 +977,12 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, SweepShared<FILT>
 
   if constexpr (SEG != 0) {
     constexpr int MBW = MB / 4;
+    constexpr int R16 = (SEG >> 2) & 3;  // 3: hot rows; 1 / 2: measurement builds only (sweep_seg)
     const uint32_t seg = ((total + 4 * 64 - 1) / (4 * 64)) * 64;  // a wave's share, whole 64-pair units
     const uint32_t s0 = min(total, wave * seg), s1 = min(total, s0 + seg);
     uint32_t* madv_w = madv + wave * MBW;
     uint8_t* mq_w = mq + wave * MBW;
-    const uint32_t nmw = sweep_seg<K, MBW, FILT, false>(a, s, madv_w, mq_w, map, nnz, total, s0, s1, lane, 0);
+    const uint32_t nmw = sweep_seg<K, MBW, FILT, false, R16>(a, s, madv_w, mq_w, map, nnz, total, s0, s1, lane, 0, hot);
     if (lane == 0) s.wsum[0][wave] = nmw;  // the row-count scan is done with wsum[0]
     __syncthreads();
     uint32_t woff = 0, nm = 0;
@@ -951,7 +1011,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, SweepShared<FILT>
         }
       }
     } else {
-      sweep_seg<K, MBW, FILT, true>(a, s, madv_w, mq_w, map, nnz, total, s0, s1, lane, base);  // rare
+      sweep_seg<K, MBW, FILT, true, R16>(a, s, madv_w, mq_w, map, nnz, total, s0, s1, lane, base, hot);  // rare
     }
     return;
   }
@@ -1033,6 +1093,9 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
   } u;
   SweepShared<FILT>& s = u.sw.s;
   uint8_t* map = u.sw.map;
+  constexpr bool kHot = ((SEG >> 2) & 3) == 3;  // hot-row sweep: the packages' windows (sweep_seg Hot16)
+  __shared__ uint64_t hot_head[kHot ? kTile : 1];
+  __shared__ uint32_t hot_tail[kHot ? kTile : 1];
   const ProbeArgs& a = fa.pa;
   if constexpr (MOVE) {
     if (blockIdx.x < fa.n_copy) {  // pipeline: the previous chunk's result move, dispatched first so the link writes overlap the tiles
@@ -1091,7 +1154,8 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
   constexpr uint32_t kQ = kBufWords > kMbWords + kTile / 8 + 16 ? kBufWords - kMbWords - kTile / 8 : 0;
   static_assert(FILT < 2 || kQ >= 16, "no room for the Maven program queue");
   const DeferQ dq{madv + kMbWords + kTile / 8, madv + kMbWords, FILT >= 2 ? kQ : 0u};
-  sweep_tile<K, MB, FILT, SEG>(fa.sa, s, madv, reinterpret_cast<uint8_t*>(madv + MB), map, t, tid, r, dq);
+  sweep_tile<K, MB, FILT, SEG>(fa.sa, s, madv, reinterpret_cast<uint8_t*>(madv + MB), map, t, tid, r, dq,
+                               Hot16{hot_head, hot_tail});
 }
 
 template <uint32_t GM, int DIAG = 0>
@@ -1115,13 +1179,21 @@ void launch_fused(uint32_t n_tiles, hipStream_t st, const FusedArgs& a) {
 
 // Table entry of variant (F, K, MB) for grammar set GM / row-filter level FILT
 // (match_variants.h: F = 0 split, 1-3 fused, 4 fused with per-wave sweep segments, 5 also
-// per-wave staging, 11-15 fused measurement builds).
+// per-wave staging, 6 the same held at 6 waves, 7 per-wave staging + segments over the hot rows
+// (DB::rows16, dpkg-only), 11-15 and 25-26 fused measurement builds).
 template <uint32_t GM, int FILT, int F, int K, int MB>
 constexpr FusedFn fused_entry() {
   if constexpr (F == 0) return nullptr;
   else if constexpr (F == 4) return &launch_fused<GM, K, MB, FILT, 0, 1, 1>;
   else if constexpr (F == 5) return &launch_fused<GM, K, MB, FILT, 0, 1, 3>;
   else if constexpr (F == 6) return &launch_fused<GM, K, MB, FILT, 0, 6, 3>;
+  else if constexpr (F == 7) {  // per-wave staging + segments over the 16-byte hot rows: dpkg-only batches
+    if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | 12>;
+    else return nullptr;
+  } else if constexpr (F == 25 || F == 26) {  // TVM_DIAG: 16-byte row loads, dpkg-only
+    if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | (F == 25 ? 4 : 8)>;
+    else return nullptr;
+  }
   // the all-grammar K <= 2 kernels are held at 5 waves per SIMD (96 VGPRs): the Maven program
   // queue (sweep_programs) took them to 97 and 4 waves
   else return &launch_fused<GM, K, MB, FILT, (F >= 10 ? F - 10 : 0), (FILT >= 2 && K <= 2 && F == 1) ? 5 : TVM_FUSED_WPE(F)>;

@@ -14,17 +14,26 @@
   X(4, 4, 2400, "fused_k4_m2400_seg")  \
   X(5, 4, 2400, "fused_k4_m2400_wseg")  \
   X(6, 2, 2400, "fused_k2_m2400_wseg6") \
-  X(6, 3, 2400, "fused_k3_m2400_wseg6")
+  X(6, 3, 2400, "fused_k3_m2400_wseg6") \
+  X(7, 4, 2400, "fused_k4_m2400_wseg_r16") \
+  X(7, 8, 2400, "fused_k8_m2400_wseg_r16")
 
 // Measurement-only variants (wrong match lists by construction): built only with
 // `make DIAG=1` (-DTVM_DIAG), never reachable in the product library.
+// F = 25 / 26 (dpkg-only): the wseg kernel (F = 5) with every pair loading 16 bytes instead of
+// its 32-byte Row - 25 at 16-byte stride (the traffic of a 16-byte row array with the same
+// indices), 26 the first half of the pair's own Row (32-byte stride: the same lines as F = 5,
+// half the bytes into the registers).  The bound on what a 16-byte row layout can gain.
 #ifdef TVM_DIAG
 #define TVM_MATCH_VARIANTS(X)      \
   TVM_MATCH_VARIANTS_PRODUCT(X)    \
   X(11, 4, 2048, "diag_no_encode") \
   X(12, 4, 2048, "diag_no_probe")  \
   X(14, 4, 2048, "diag_no_sweep")  \
-  X(15, 4, 2048, "diag_stage_only")
+  X(15, 4, 2048, "diag_stage_only") \
+  X(25, 4, 2400, "diag_row16_k4")  \
+  X(25, 8, 2400, "diag_row16_k8")  \
+  X(26, 4, 2400, "diag_row16s_k4")
 #else
 #define TVM_MATCH_VARIANTS(X) TVM_MATCH_VARIANTS_PRODUCT(X)
 #endif
@@ -44,7 +53,10 @@ constexpr int kNumTuned = 0 TVM_MATCH_VARIANTS(TVM_VARIANT_COUNT_);
 // sweep segments are fastest for dpkg-only batches (C2 0.485 -> 0.469 ms); for the filtered
 // grammar sets (rpm/apk/library rows, uneven per-pair cost) the shared K=2 sweep stays fastest
 // (C3 0.257 ms against 0.34-0.36 ms in segments).
-constexpr int kAutoVariant = 6;          // fused_k4_m2400_wseg
+// Since the 16-byte hot rows (DB::rows16): the same kernel sweeping them, K = 4 (C2 sweep,
+// profiles/row16/sweep_c2.txt: 0.3754 ms against 0.3836; K = 8 holds 115 VGPRs, 4 waves per SIMD
+// instead of 5: 0.4232 ms).  fused_k4_m2400_wseg stays in the list as its A/B partner.
+constexpr int kAutoVariant = 9;          // fused_k4_m2400_wseg_r16
 constexpr int kAutoVariantFiltered = 1;  // fused_k2_m2048
 // OS grammar sets with row filters (rpm / apk: no library rows): per-wave staging + segments
 // at 6 waves, K = 2 (round 5 sweep, profiles/r05/sweep_c5.txt: C5 2.317 -> 2.283 ms)

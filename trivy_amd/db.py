@@ -84,6 +84,26 @@ class DB:
         return dict(zip(["rows", "pad_rows", "interval_rows", "class0_dup_rows", "inline_rows", "split_keys"],
                         list(out)))
 
+    def row16_stats(self):
+        """The dpkg grammar's 16-byte hot rows (tvm_db_row16_stats): keys_by_p[P] = dpkg keys whose
+        bounds share a P-byte prefix, hot_rows = rows a hot row expresses, fallback_rows = the rest."""
+        if not self._finalized:
+            raise ValueError("row16_stats: the DB is not finalized")
+        out = (ctypes.c_uint64 * 10)()
+        lib().tvm_db_row16_stats(self.h, out)
+        return {"keys_by_p": list(out[:8]), "hot_rows": int(out[8]), "fallback_rows": int(out[9])}
+
+    def row16_eval(self, bucket, name, version):
+        """tvm_row16_eval_host: [(path, matches)] per row of key (bucket, name) for an installed
+        version - path 0 the hot row decided, 1 a window tie, 2 a fall-back row; None: no such key."""
+        name, version = name.encode(), version.encode()
+        n = lib().tvm_row16_eval_host(self.h, bucket.encode(), name, len(name), version, len(version), None, None, 0)
+        if n < 0:
+            return None
+        path, res = (ctypes.c_uint8 * max(n, 1))(), (ctypes.c_uint8 * max(n, 1))()
+        lib().tvm_row16_eval_host(self.h, bucket.encode(), name, len(name), version, len(version), path, res, n)
+        return [(int(path[i]), int(res[i])) for i in range(n)]
+
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         if h and _lib._lib is not None:
