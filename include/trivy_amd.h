@@ -644,6 +644,24 @@ int tvm_match_filter_ignored(tvm_engine* e, tvm_batch* b, uint32_t* triples, uin
 int tvm_match_filter_time(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* o, int steps, double* ms, char* err,
                           size_t errlen);
 
+/* ---- severity / status filter inside the pipelined pass --------------------------------
+ * After tvm_pipeline_prepare: the following passes return only findings that pass
+ * o->severity_mask and o->ignore_status_mask (filter.go:113-120), tested on the GPU before
+ * the result move, so only survivors cross the link.  Both tests read what FillInfo decides
+ * from the advisory alone, and filterVulnerabilities applies them before the ignore file and
+ * the dedup: every later step of result.Filter sees the findings it would have seen anyway.
+ * A non-NULL o always runs the filter kernel, also when it keeps everything; o = NULL clears
+ * the filter, and so does a new tvm_pipeline_prepare.  With a filter set, tvm_pipeline_run's
+ * *n_matches stays the raw match count (and the pass still needs match_cap >= it), while
+ * tvm_pipeline_result, tvm_pipeline_result_raw and tvm_pipeline_vulns return the kept lists
+ * (n = the kept count) and tvm_pipeline_stats[1] counts the kept findings' bytes.
+ * TVM_EINVAL: no prepared pipeline, a batch with Red Hat packages (redhat.go:146-187 takes a
+ * merged group's Status and Severity from its first member, so the per-CVE merge must see the
+ * unfiltered lists), or o->ignore / o->n_vex set (those need whole results: tvm_match_filter). */
+int tvm_pipeline_set_filter(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* o, char* err, size_t errlen);
+/* out = {raw matches, kept} of the last completed pass (equal without a filter). */
+int tvm_pipeline_filter_stats(tvm_batch* b, uint64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

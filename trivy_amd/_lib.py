@@ -268,6 +268,8 @@ _SIG = [
                                             ctypes.POINTER(RawStr), ctypes.POINTER(RawStr)]),
     ("tvm_match_filter_time", ctypes.c_int, [_P, _P, ctypes.POINTER(FilterOpts), ctypes.c_int,
                                              ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_size_t]),
+    ("tvm_pipeline_set_filter", ctypes.c_int, [_P, _P, ctypes.POINTER(FilterOpts), ctypes.c_char_p, ctypes.c_size_t]),
+    ("tvm_pipeline_filter_stats", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
 ]
 
 EXPORTED = [s[0] for s in _SIG]

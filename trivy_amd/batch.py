@@ -326,6 +326,25 @@ class MatchBatch:
         return {"h2d_bytes": out[0], "d2h_bytes": out[1], "chunks": out[2], "transport_form": bool(out[3]),
                 "encode_ms": out[4] / 1e3, "prepare_ms": prep.value / 1e3}
 
+    def pipeline_set_filter(self, opts):
+        """The following pipeline_run() passes return only the findings that pass opts'
+        severities and ignored statuses (filter_opts(); no ignore rules or VEX), tested on the
+        GPU before the result move; None clears the filter - tvm_pipeline_set_filter."""
+        e = errbuf()
+        rc = lib().tvm_pipeline_set_filter(self.engine.h, self.h, ctypes.byref(opts) if opts is not None else None, e,
+                                           len(e))
+        if rc == 3:  # TVM_EINVAL: a refusal (the filter set before stays as it was)
+            raise ValueError(f"tvm_pipeline_set_filter: {e.value.decode() or 'invalid argument'}")
+        self._check(rc, e, "tvm_pipeline_set_filter")
+        return self
+
+    def pipeline_filter_stats(self):
+        """(raw matches, kept findings) of the last completed pass."""
+        out = (ctypes.c_uint64 * 2)()
+        if lib().tvm_pipeline_filter_stats(self.h, out):
+            raise RuntimeError("tvm_pipeline_filter_stats: no completed pass")
+        return out[0], out[1]
+
     # ---- FillInfo fused behind the match list (tvm_match_fill*) ----
     def fill(self, sync=True):
         """Enqueue FillInfo over the device match list (after launch())."""

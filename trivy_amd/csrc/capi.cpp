@@ -56,11 +56,12 @@ struct tvm_engine {
   std::unique_ptr<FillEngine> fill;
   std::mutex rh_mu;                   // lazily built Red Hat fixed-version ranks (device)
   uint2* rh_rank = nullptr;  // per advisory {vulnerability-ID rank, rpm rank of FixedVersion} (Red Hat merge)
+  std::mutex cls_mu;         // lazily built advisory classes of the pipelined pass's filter (device)
+  uint16_t* cls = nullptr;   // per advisory: severity index | status << 8 (prefilter.hip)
   ~tvm_engine() {
-    if (rh_rank) {
-      (void)hipSetDevice(device);
-      (void)hipFree(rh_rank);
-    }
+    if (rh_rank || cls) (void)hipSetDevice(device);
+    if (rh_rank) (void)hipFree(rh_rank);
+    if (cls) (void)hipFree(cls);
   }
   tvm_db* db = nullptr;
   int device = 0;
@@ -93,8 +94,9 @@ struct tvm_batch {
   bool merged = false;                 // the merged list (rh) is the current match list
   std::unique_ptr<Pipeline> pipe;      // tvm_pipeline_* state
   uint32_t pkg_base = 0;               // tvm_batch_set_package_base
-  uint64_t pipe_total = 0;
-  bool pipe_ok = false;                // the pipeline's last pass completed (its result is valid)
+  uint64_t pipe_total = 0;             // raw matches of the last pass
+  uint64_t pipe_kept = 0;              // findings in its result (= pipe_total without a filter)
+  bool pipe_ok = false;               // the pipeline's last pass completed (its result is valid)
   int64_t pipe_errp = -1;              // that pass's first poisoned package (-1: none)
   RedHatMerge pipe_rh;                 // the per-CVE merge over a pipelined pass's list (tvm_pipeline_vulns)
   uint64_t pipe_runs = 0, pipe_wide_for = ~0ull;  // passes run; the pass pipe_wide was widened for
@@ -453,6 +455,10 @@ int tvm_engine_swap(tvm_engine* e, tvm_db* db, char* err, size_t errlen) {
   if (e->rh_rank) {
     (void)hipFree(e->rh_rank);
     e->rh_rank = nullptr;
+  }
+  if (e->cls) {  // the new tables' classes are built by their first filtered pass
+    (void)hipFree(e->cls);
+    e->cls = nullptr;
   }
   return TVM_OK;
 }
@@ -1598,6 +1604,15 @@ int tvm_match_filter_time(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* o,
 
 namespace {
 bool batch_has_redhat(const tvm_batch* b, const DB& db);
+
+// The advisory classes of the engine's current tables (prefilter.hip), built by the first
+// filtered pass after open / swap.  Callers hold the engine's lock (shared).
+bool ensure_cls(tvm_engine* e, std::string& err) {
+  std::lock_guard<std::mutex> g(e->cls_mu);
+  if (e->cls) return true;
+  e->cls = build_class_table(*e->fill, e->eng->stream(), err);
+  return e->cls != nullptr;
+}
 }  // namespace
 
 int tvm_pipeline_prepare(tvm_engine* e, tvm_batch* b, uint64_t match_cap, uint32_t chunk_packages, uint32_t flags,
@@ -1611,7 +1626,7 @@ int tvm_pipeline_prepare(tvm_engine* e, tvm_batch* b, uint64_t match_cap, uint32
     return TVM_EINVAL;
   }
   b->pipe.reset(new Pipeline());
-  b->pipe_total = 0;  // no valid pass of the new pipeline yet
+  b->pipe_total = b->pipe_kept = 0;  // no valid pass of the new pipeline yet (and no filter: a new Pipeline)
   b->pipe_ok = false;
   b->pipe_rh.forget_tiles();
   b->pipe_wide_for = ~0ull;
@@ -1639,10 +1654,14 @@ int tvm_pipeline_run(tvm_engine* e, tvm_batch* b, uint64_t* n_matches, int64_t* 
   uint64_t total = 0, bits = 0;
   int64_t ep = -1;
   const auto t0 = std::chrono::steady_clock::now();
-  b->pipe_total = 0;  // a failed pass leaves no result behind
+  b->pipe_total = b->pipe_kept = 0;  // a failed pass leaves no result behind
   b->pipe_ok = false;
   b->pipe_wide_for = ~0ull;
-  const bool ok = b->pipe->run(*e->eng, b->hb, total, ep, bits, msg);
+  if (b->pipe->filtered() && !ensure_cls(e, msg)) {
+    set_err(err, errlen, "tvm_pipeline_run: " + msg);
+    return TVM_EDEVICE;
+  }
+  const bool ok = b->pipe->run(*e->eng, b->hb, total, ep, bits, msg, e->cls, e->fill->dev().n_advs);
   const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (!ok) {
     set_err(err, errlen, msg);
@@ -1661,8 +1680,53 @@ int tvm_pipeline_run(tvm_engine* e, tvm_batch* b, uint64_t* n_matches, int64_t* 
     set_err(err, errlen, "tvm_pipeline_run: match buffer too small (prepare with match_cap >= n_matches)");
     return TVM_EINVAL;
   }
+  b->pipe_kept = b->pipe->kept();
   b->pipe_ok = true;
   b->pipe_errp = ep;
+  return TVM_OK;
+}
+
+int tvm_pipeline_set_filter(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* o, char* err, size_t errlen) {
+  if (!e || !b) return TVM_EINVAL;
+  if (!b->pipe) {
+    set_err(err, errlen, "tvm_pipeline_set_filter: tvm_pipeline_prepare the batch first");
+    return TVM_EINVAL;
+  }
+  std::shared_lock<std::shared_mutex> lk(e->mu);
+  if (!bind(b, e)) {
+    set_err(err, errlen, kStale);
+    return TVM_EINVAL;
+  }
+  if (!o) {
+    b->pipe->clear_filter();
+    return TVM_OK;
+  }
+  if (o->ignore || o->n_vex) {
+    set_err(err, errlen, "tvm_pipeline_set_filter: ignore rules and VEX statements need whole results "
+                         "(tvm_match_filter); only the severity and status masks are tested in the pass");
+    return TVM_EINVAL;
+  }
+  if (batch_has_redhat(b, e->eng->db())) {
+    // redhat.go:146-187: a merged group takes Status and Severity from its first member, so
+    // the merge has to see the unfiltered lists
+    set_err(err, errlen, "tvm_pipeline_set_filter: the batch holds Red Hat packages, whose per-CVE merge reads "
+                         "the unfiltered lists");
+    return TVM_EINVAL;
+  }
+  std::string msg;
+  (void)hipSetDevice(e->device);
+  if (!ensure_cls(e, msg)) {
+    set_err(err, errlen, "tvm_pipeline_set_filter: " + msg);
+    return TVM_EDEVICE;
+  }
+  b->pipe->set_filter(o->severity_mask, o->ignore_status_mask);
+  return TVM_OK;
+}
+
+int tvm_pipeline_filter_stats(tvm_batch* b, uint64_t out[2]) {
+  if (!b || !out || !b->pipe || !b->pipe_ok) return TVM_EINVAL;
+  out[0] = b->pipe_total;
+  out[1] = b->pipe_kept;
   return TVM_OK;
 }
 
@@ -1671,9 +1735,9 @@ int tvm_pipeline_result(tvm_batch* b, const uint32_t** adv, const uint32_t** row
   if (adv && b->pipe->packed()) {  // widen the 3-byte indices once per pass (host side, after the pass)
     if (b->pipe_wide_for != b->pipe_runs) {
       const uint8_t* p = reinterpret_cast<const uint8_t*>(b->pipe->adv());
-      b->pipe_wide.resize(b->pipe_total);
+      b->pipe_wide.resize(b->pipe_kept);
       uint32_t* w = b->pipe_wide.data();
-      range_for(b->pipe_total, size_t(1) << 18, [&](size_t i0, size_t i1) {
+      range_for(b->pipe_kept, size_t(1) << 18, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++) w[i] = uint32_t(p[3 * i]) | uint32_t(p[3 * i + 1]) << 8 | uint32_t(p[3 * i + 2]) << 16;
       });
       b->pipe_wide_for = b->pipe_runs;
@@ -1683,7 +1747,7 @@ int tvm_pipeline_result(tvm_batch* b, const uint32_t** adv, const uint32_t** row
     *adv = b->pipe->adv();
   }
   if (row_end) *row_end = b->pipe->row_end();
-  if (n_matches) *n_matches = b->pipe_total;
+  if (n_matches) *n_matches = b->pipe_kept;
   return TVM_OK;
 }
 
@@ -1693,7 +1757,7 @@ int tvm_pipeline_result_raw(tvm_batch* b, const void** adv, uint32_t* width, con
   if (adv) *adv = b->pipe->adv();
   if (width) *width = b->pipe->packed() ? 3 : 4;
   if (row_end) *row_end = b->pipe->row_end();
-  if (n_matches) *n_matches = b->pipe_total;
+  if (n_matches) *n_matches = b->pipe_kept;
   return TVM_OK;
 }
 
@@ -2185,7 +2249,7 @@ int tvm_pipeline_vulns(tvm_engine* e, tvm_batch* b, tvm_vuln_set* out, char* err
     templates(e->db);
     auto st = std::make_unique<VulnSetStore>();
     set_out(e->db, st.release(), b->pipe->row_end(), b->hb.pk.size(), b->pkg_base,
-            reinterpret_cast<const uint8_t*>(b->pipe->adv()), b->pipe->packed() ? 3u : 4u, b->pipe_total, out);
+            reinterpret_cast<const uint8_t*>(b->pipe->adv()), b->pipe->packed() ? 3u : 4u, b->pipe_kept, out);
     return TVM_OK;
   }
   // Red Hat packages report merged groups (redhat.go:146-187): the pass's whole match list is

@@ -26,6 +26,30 @@ void launch_order(uint32_t n_tiles, hipStream_t st, const OrderArgs& a);
 void launch_copy_out(hipStream_t st, const CopyOutArgs& a);  // engine.h copy_out_tiles as its own kernel
 void release_encoders();  // the transport-form encoders kept between batches (tvm_shutdown)
 
+// The pipelined pass's severity / status filter (prefilter.hip): one chunk's match segments
+// compacted in place to the findings that pass filter.go:113-120, ahead of the chunk's result
+// move.  cls: per DB advisory `severity index (0..4, 5 = outside SeverityNames) | status << 8`.
+struct PrefilterArgs {
+  TileDir* dir = nullptr;   // dir[t].count becomes the tile's kept count
+  uint32_t* pkg = nullptr;  // the match columns (compacted inside each tile's segment)
+  uint32_t* adv = nullptr;
+  const uint16_t* cls = nullptr;
+  uint32_t n_cls = 0;
+  uint32_t sev_mask = 0;     // bit i: SeverityNames[i] passes
+  uint32_t status_mask = 0;  // bit s: status s is dropped
+  uint32_t t0 = 0, t1 = 0;   // the chunk's tiles
+  uint64_t cap = 0;          // match capacity (a tile beyond it is left alone)
+  unsigned long long* ctl = nullptr;  // the pass's control block: ctl[kCtlKept] += kept
+};
+// Word of the 64-byte control block (engine.h DevMatches::ctl; [0..3] are the match kernels')
+// that counts a filtered pass's kept findings: it rides the pass's one control-block copy.
+constexpr int kCtlKept = 4;
+void launch_prefilter(hipStream_t st, const PrefilterArgs& a);
+class FillEngine;
+// The class table of every advisory of `fill`'s tables (device; hipFree): FillInfo's batch
+// kernel over the identity list, narrowed to 16 bits.  Synchronises `st`.  nullptr + err on failure.
+uint16_t* build_class_table(FillEngine& fill, hipStream_t st, std::string& err);
+
 
 // One batch's pipeline state.  prepare() builds the batch's pinned transport form (or a
 // pinned copy of its raw arrays), sizes the device batch, the match buffers and the pinned result buffers; run() then
@@ -49,7 +73,20 @@ class Pipeline {
                bool packed, std::string& err);
   // One pass.  total = matches (> match_cap: nothing valid, re-prepare with a larger cap);
   // err_pkg = first poisoned package or -1.
-  bool run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& err_pkg, uint64_t& err_bits, std::string& err);
+  // cls / n_cls: the engine's advisory class table (prefilter.hip), read when a filter is set
+  bool run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& err_pkg, uint64_t& err_bits, std::string& err,
+           const uint16_t* cls = nullptr, uint32_t n_cls = 0);
+  // The following passes return only the findings of these severities whose status is not
+  // ignored (tested per chunk on the GPU, before the result move); cleared by clear_filter().
+  // Without a filter a pass enqueues exactly what it did before filters existed.
+  void set_filter(uint32_t sev_mask, uint32_t status_mask) {
+    filter_ = true;
+    sev_mask_ = sev_mask & 0x1Fu;
+    status_mask_ = status_mask;
+  }
+  void clear_filter() { filter_ = false; }
+  bool filtered() const { return filter_; }
+  uint64_t kept() const { return kept_; }  // the last pass's result length (= total without a filter)
   // 4-byte indices, or 3-byte ones when packed()
   const uint32_t* adv() const { return adv_h_; }
   bool packed() const { return packed_; }
@@ -105,6 +142,9 @@ class Pipeline {
   uint64_t wire_bytes_ = 0;                       // size of wire_h_ / wire_d_
   uint64_t adv_units_ = 0, row_end_units_ = 0;    // 16-byte units of adv_h_ / row_end_h_ (guards)
   bool prepared_ = false;
+  bool filter_ = false;
+  uint32_t sev_mask_ = 0, status_mask_ = 0;
+  uint64_t kept_ = 0;
   bool packed_ = false;  // no Engine pointer: the batch may outlive a hot swap (the C-ABI checks the generation)
 };
 

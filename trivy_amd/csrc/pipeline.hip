@@ -328,13 +328,18 @@ bool Pipeline::prepare(Engine& eng, const HostBatch& hb, uint64_t match_cap, uin
 }
 
 bool Pipeline::run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& err_pkg, uint64_t& err_bits,
-                   std::string& err) {
+                   std::string& err, const uint16_t* cls, uint32_t n_cls) {
   total = 0;
+  kept_ = 0;
   err_pkg = -1;
   err_bits = 0;
   h2d_ = d2h_ = 0;
   if (!prepared_ || db_.n != hb.pk.size()) {
     err = "pipeline: prepare() the batch first";
+    return false;
+  }
+  if (filter_ && !cls) {
+    err = "pipeline: a filter is set but the advisory class table is missing";
     return false;
   }
   (void)hipSetDevice(dev_);
@@ -438,6 +443,24 @@ bool Pipeline::run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& e
     const CopyOutArgs prev_co = prev >= 0 ? copy_args(uint32_t(prev)) : CopyOutArgs{};
     if (!eng.launch_tiles(db_, m_, t0, t1, s_k_, s_k_, nullptr, err, prev >= 0 ? &prev_co : nullptr)) return false;
     if (prev >= 0 && !rowend_up(uint32_t(prev))) return false;
+    if (filter_) {
+      // chunk c's segments are compacted to the findings that pass, behind its match launch and
+      // ahead of whatever moves its result out (chunk c + 1's launch, or the last copy-out below)
+      PrefilterArgs pa;
+      pa.dir = m_.dir;
+      pa.pkg = m_.pkg;
+      pa.adv = m_.adv;
+      pa.cls = cls;
+      pa.n_cls = n_cls;
+      pa.sev_mask = sev_mask_;
+      pa.status_mask = status_mask_;
+      pa.t0 = t0;
+      pa.t1 = t1;
+      pa.cap = cap_;
+      pa.ctl = m_.ctl;
+      launch_prefilter(s_k_, pa);
+      if (!ok(hipGetLastError(), "prefilter kernel launch", err)) return false;
+    }
     if (trace) std::fprintf(stderr, "pipe c%u match %.1f us\n", c, us());
     prev = c;
   }
@@ -450,7 +473,10 @@ bool Pipeline::run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& e
   if (trace) std::fprintf(stderr, "pipe ctl queued %.1f us\n", us());
   if (!ok(hipStreamSynchronize(s_k_), "pipeline", err) || !ok(hipStreamSynchronize(s_d2h_), "pipeline", err)) return false;
   if (trace) std::fprintf(stderr, "pipe done %.1f us\n", us());
-  d2h_ = uint64_t(n) * 4 + std::min<uint64_t>(ctl_h_[0], cap_) * (packed_ ? 3 : 4);
+  // the overflow rule stays on the raw count (the match buffer holds raw matches); the result
+  // and its link bytes are the kept findings
+  kept_ = filter_ ? ctl_h_[kCtlKept] : ctl_h_[0];
+  d2h_ = uint64_t(n) * 4 + std::min<uint64_t>(kept_, cap_) * (packed_ ? 3 : 4);
   total = ctl_h_[0];
   err_pkg = ctl_h_[1] ? int64_t(n - ctl_h_[1]) : -1;
   err_bits = ctl_h_[3];
