@@ -157,9 +157,18 @@ void tvm_db_row16_stats(const tvm_db* db, uint64_t out[10]);
 /* The hot-row compare on the host: `version` against every row of key (bucket, name), in row order.
  * path[i]: 0 the hot row decided, 1 its window tied (the 32-byte row decided), 2 a fall-back row;
  * result[i]: 1 the row matches.  Returns the key's row count (at most `cap` entries are written),
- * -1 when the bucket or the key is absent. */
+ * -1 when the bucket or the key is absent, -2 when the two forms of the pair test (common.h
+ * row16_test and row16_test_lex, both run on every pair written) disagree on a pair. */
 int tvm_row16_eval_host(const tvm_db* db, const char* bucket, const char* name, size_t name_len, const char* version,
                         size_t version_len, uint8_t* path, uint8_t* result, size_t cap);
+/* One pair of the hot-row test on the host, the row given raw (Row16: adv, tail, head): the
+ * installed sort key (`valid` = 0: the version did not parse) behind the slot prefix word pfx.
+ * lex = 0: common.h row16_test (the parent's sweep), 1: row16_test_lex (the REC sweep).
+ * Returns bit 0 = the row matches (meaningful when bit 1 is clear), bit 1 = the pair stays open
+ * (the full row decides); -1 on bad arguments.  tvm_row16_eval_host returns -2 when the two
+ * forms disagree on a pair of the key. */
+int tvm_row16_pair_host(const uint8_t* key, size_t key_len, int valid, uint64_t pfx, uint32_t row_adv, uint32_t row_tail,
+                        uint64_t row_head, int lex);
 
 /* ---- device engine -------------------------------------------------------------------- */
 /* Uploads the finalized tables to HIP device `device`.  `db` must outlive the engine. */
@@ -322,6 +331,10 @@ int tvm_version_class(int grammar, const char* s, size_t n);
  * for the dpkg grammar).  Key length, -1 when the version does not parse, -2 when the
  * kernel hands the version to the generic encoder. */
 int tvm_deb_fast_key_host(const char* s, size_t n, uint32_t shift, uint8_t* out, size_t cap);
+/* The same run on the caller's own key buffer, as a lane's LDS slot: kb (at least 44 bytes,
+ * the lane stride) is written in place, so a test that pre-fills it sees every byte the
+ * builder touched.  Returns as tvm_deb_fast_key_host (the length also for kb[0, len)). */
+int tvm_deb_fast_key_slot_host(const char* s, size_t n, uint32_t shift, uint8_t* kb, size_t kb_len);
 /* Host-side compare.IsVulnerable through the load-time interval compiler (tests): 1/0, -1
  * when the advisory JSON does not decode.  Maven: the rows the product builds - intervals for
  * an advisory whose bounds are all numeric, else the pairwise program - so it mirrors the

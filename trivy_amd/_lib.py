@@ -137,6 +137,8 @@ _SIG = [
     ("tvm_db_row16_stats", None, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tvm_row16_eval_host", ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
+    ("tvm_row16_pair_host", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int]),
     ("tvm_engine_open", _P, [_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_engine_close", None, [_P]),
     ("tvm_engine_swap", ctypes.c_int, [_P, _P, ctypes.c_char_p, ctypes.c_size_t]),
@@ -232,6 +234,8 @@ _SIG = [
     ("tvm_engine_dropin_stats", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("tvm_deb_fast_key_host", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,
                                              ctypes.c_size_t]),
+    ("tvm_deb_fast_key_slot_host", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,
+                                                  ctypes.c_size_t]),
     ("tvm_db_advisory_vuln_id", ctypes.c_char_p, [_P, ctypes.c_uint32]),
     ("tvm_version_class", ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_lib_is_vulnerable_host", ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,

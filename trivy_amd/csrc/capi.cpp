@@ -349,10 +349,15 @@ int tvm_row16_eval_host(const tvm_db* db, const char* bucket, const char* name, 
   uint64_t ph;
   uint32_t pt;
   row16_pkg(k[0], k[1], k[2], kl, P, row16_prefix_cmp(k[0], kl, pfx), valid, ph, pt);
+  uint64_t lh;  // the REC sweep's form of the same test: both must agree on every pair
+  uint32_t lt;
+  row16_pkg_lex(k[0], k[1], k[2], kl, P, row16_prefix_cmp(k[0], kl, pfx), valid, lh, lt);
   for (uint32_t i = 0; i < cnt && i < cap; i++) {
     const Row16& h = d.rows16[rb + i];
-    bool slow = false;
+    bool slow = false, slow_lex = false;
     bool m = row16_test(ph, pt, h, slow);
+    const bool m_lex = row16_test_lex(lh, lt, h, slow_lex);
+    if (slow != slow_lex || (!slow && m != m_lex)) return -2;
     if (slow) {
       const Row& r = d.rows[rb + i];
       const RowOff& o = d.row_off[rb + i];
@@ -371,6 +376,30 @@ int tvm_row16_eval_host(const tvm_db* db, const char* bucket, const char* name, 
     if (result) result[i] = m ? 1 : 0;
   }
   return int(cnt);
+}
+
+int tvm_row16_pair_host(const uint8_t* key, size_t key_len, int valid, uint64_t pfx, uint32_t row_adv, uint32_t row_tail,
+                        uint64_t row_head, int lex) {
+  if ((!key && key_len) || key_len > 0x3FFF) return -1;
+  uint64_t k[3] = {0, 0, 0};  // the 24-byte big-endian head, as the probe keeps it
+  for (size_t i = 0; i < key_len && i < 24; i++) k[i / 8] |= uint64_t(key[i]) << (8 * (7 - i % 8));
+  const uint32_t kl = valid ? uint32_t(key_len) : 0u, P = uint32_t(pfx) & 0xFFu;
+  if (!valid) k[0] = k[1] = k[2] = 0;
+  Row16 r;
+  r.adv = row_adv;
+  r.tail = row_tail;
+  r.head = row_head;
+  uint64_t ph;
+  uint32_t pt;
+  bool slow = false, m;
+  if (lex) {
+    row16_pkg_lex(k[0], k[1], k[2], kl, P, row16_prefix_cmp(k[0], kl, pfx), valid != 0, ph, pt);
+    m = row16_test_lex(ph, pt, r, slow);
+  } else {
+    row16_pkg(k[0], k[1], k[2], kl, P, row16_prefix_cmp(k[0], kl, pfx), valid != 0, ph, pt);
+    m = row16_test(ph, pt, r, slow);
+  }
+  return (m ? 1 : 0) | (slow ? 2 : 0);
 }
 
 const char* tvm_db_advisory_vuln_id(const tvm_db* db, uint32_t adv) {
@@ -1125,6 +1154,18 @@ int tvm_deb_fast_key_host(const char* s, size_t n, uint32_t shift, uint8_t* out,
   if (st == FAST_FALLBACK) return -2;
   for (uint32_t i = 0; i < len && i < cap; i++) out[i] = kb[i];
   return int(len);
+}
+
+int tvm_deb_fast_key_slot_host(const char* s, size_t n, uint32_t shift, uint8_t* kb, size_t kb_len) {
+  if (!s || !kb || n > 4096 || shift > 3 || kb_len < kFastKeyStride) return -3;
+  uint8_t tab[128];
+  for (uint32_t c = 0; c < 128; c++) tab[c] = deb_fast_code(c);
+  std::vector<uint32_t> buf((shift + n) / 4 + 4, 0xA5A5A5A5u);  // padded like the LDS stage window
+  uint8_t* b = reinterpret_cast<uint8_t*>(buf.data()) + shift;
+  std::memcpy(b, s, n);
+  uint32_t len = 0;
+  const uint32_t st = deb_fast_key(b, uint32_t(n), kb, tab, len);
+  return st == FAST_INVALID ? -1 : st == FAST_FALLBACK ? -2 : int(len);
 }
 
 int tvm_lib_is_vulnerable_host(int grammar, const char* ver, size_t ver_len, const char* advisory_json,

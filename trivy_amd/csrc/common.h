@@ -342,4 +342,37 @@ TVM_HD bool row16_test(uint64_t ph, uint32_t pt, const Row16& r, bool& slow) {
   return m || (r.adv & ROW_ALWAYS);
 }
 
+// ---- the same test as one lexicographic compare (the REC sweep, match_kernel.h sweep_seg) ----
+// A row is the 96-bit value (head, tail): window bytes over the length code, so "equal windows, the
+// shorter key first" is part of the order.  DB::row16_build gives a row without a bound the window
+// R16_INF_HEAD / R16_INF_TAIL (above every bounded row: the code of a bounded row is <= 12) and a
+// FALLBACK row the tail R16_FALLBACK_TAIL; row16_test reads the code byte only, so both tests read
+// the same rows.  The package's side (row16_pkg_lex, once per package) folds the prefix outcome and
+// the validity into its value A, and pair (A, B) matches iff A <= B:
+//   valid, equal prefix   (window head, window tail bytes | na + 1; 12 | R16_LEX_TIE for na > 11)
+//                          - with equal windows na + 1 <= nb iff the package's key is the shorter
+//   valid, below          (0, 0): at or below every row, the bound that equals the prefix (0, 0) too
+//   valid, above          (~0, 0xFFFFFF0D): above every bounded row, below the unbounded one
+//   invalid               (~0, ~0): above every row
+// A window tie with both keys longer (slow: the full Row decides) is the one pair whose tails differ
+// in exactly R16_LEX_TIE: the package's 12 | 16 against the row's 12 (no other code of a valid package has
+// that bit, and of the row codes only INF and FALLBACK, which differ in higher bits too).
+constexpr uint64_t R16_INF_HEAD = ~0ull;
+enum : uint32_t { R16_INF_TAIL = 0xFFFFFF00u | R16_INF, R16_FALLBACK_TAIL = 0xFFFFFFFFu, R16_LEX_TIE = 0x10,
+                  R16_LEX_ABOVE = 0xFFFFFF0Du };
+TVM_HD void row16_pkg_lex(uint64_t k0, uint64_t k1, uint64_t k2, uint32_t kl, uint32_t P, uint32_t outcome, bool valid,
+                          uint64_t& head, uint32_t& tail) {
+  row16_window(k0, k1, k2, kl, P, head, tail);
+  const uint32_t na = tail & R16_LEN_MASK;
+  tail = (tail & 0xFFFFFF00u) | (na > kRow16Window ? (kRow16Window + 1) | R16_LEX_TIE : na + 1);
+  if (outcome == R16_PFX_BELOW) head = 0, tail = 0;
+  if (outcome == R16_PFX_ABOVE) head = ~0ull, tail = R16_LEX_ABOVE;
+  if (!valid) head = ~0ull, tail = ~0u;
+}
+TVM_HD bool row16_test_lex(uint64_t ph, uint32_t pt, const Row16& r, bool& slow) {
+  const bool eqh = ph == r.head;
+  slow = r.tail == R16_FALLBACK_TAIL || (eqh && (pt ^ r.tail) == R16_LEX_TIE);
+  return ph < r.head || (eqh && pt <= r.tail) || (r.adv & ROW_ALWAYS);
+}
+
 }  // namespace tvm

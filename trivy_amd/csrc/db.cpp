@@ -859,10 +859,10 @@ uint64_t DB::row16_build(uint32_t rb, uint32_t cnt) {
     Row16 h{};
     h.adv = r.adv;
     if (!plain(r)) {
-      h.tail = R16_FALLBACK;
+      h.tail = R16_FALLBACK_TAIL;
       row16_stats_[9]++;
     } else {
-      if (r.hi_len & KEY_INF) h.tail = R16_INF;
+      if (r.hi_len & KEY_INF) h.head = R16_INF_HEAD, h.tail = R16_INF_TAIL;  // above every bounded row (row16_test_lex)
       else row16_window(r.hi_pre0, r.hi_pre1, r.hi_pre2, r.hi_len & KEY_LEN_MASK, P, h.head, h.tail);
       row16_stats_[8]++;
     }
@@ -904,7 +904,7 @@ void DB::build_index() {
   n_rows_total = rows.size();
   // hot rows: R16_FALLBACK wherever no dpkg key's run is (other grammars, pad rows)
   Row16 fb{};
-  fb.tail = R16_FALLBACK;
+  fb.tail = R16_FALLBACK_TAIL;
   rows16.assign(rows.size(), fb);
   for (uint64_t& x : row16_stats_) x = 0;
   std::vector<uint64_t> key_pfx(keys.size(), 0);

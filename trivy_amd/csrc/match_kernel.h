@@ -836,11 +836,18 @@ __device__ __forceinline__ uint32_t sweep(const SweepArgs& a, SweepShared<FILT>&
 // construction): a pair loads 16 bytes, not its Row - 1: rows[] read as a 16-byte array at the
 // pair's row index, 2: the first half of the pair's Row.  The bound is read as a 16-byte head of a
 // key no longer than its head, so no pair leaves the branch-free path or reads the key arena.
+// REC (with R16 = 3): the package's side by nz rank, not by tile package - sweep_tile writes the
+// window of the r-th package that has rows (the value common.h row16_pkg_lex gives) to head[r] /
+// tail[r] next to nz_rd[r] - so a pair reads map[j], then its window and row offset in one level
+// instead of nz_q / nz_rd, then head / tail; tests its row with one lexicographic compare
+// (row16_test_lex) and reads its package index only where it matched (or stays open).  (One
+// 16-byte record per rank with the row offset inside took 1 KB more LDS, 32192 B: the fifth
+// workgroup of a CU no longer fitted and the pass ran 0.425 ms against 0.388)
 struct Hot16 {
-  uint64_t* head;  // per tile package: common.h row16_pkg
+  uint64_t* head;  // per tile package: common.h row16_pkg (REC: per nz rank, row16_pkg_lex)
   uint32_t* tail;
 };
-template <int K, int MBW, int FILT, bool DIRECT, int R16 = 0>
+template <int K, int MBW, int FILT, bool DIRECT, int R16 = 0, bool REC = false>
 __device__ __forceinline__ uint32_t sweep_seg(const SweepArgs& a, const SweepShared<FILT>& s, uint32_t* madv,
                                               uint8_t* mq, const uint8_t* map, uint32_t nnz, uint32_t total,
                                               uint32_t s0, uint32_t s1, uint32_t lane, unsigned long long base,
@@ -849,6 +856,53 @@ __device__ __forceinline__ uint32_t sweep_seg(const SweepArgs& a, const SweepSha
   const uint32_t pbase = s.tile * kTile;
   const uint32_t shift = map_shift(total);
   uint32_t nm = 0;
+  // one 64-pair group's matches, in pair order behind the nm placed so far: to the output (DIRECT)
+  // or the wave's LDS buffer while it has room; q() gives the pair's tile package (matches only)
+  auto place = [&](bool m, uint32_t adv, auto q) {
+    const unsigned long long bal = __ballot(m);
+    if (m) {
+      const uint32_t pos = nm + uint32_t(__popcll(bal & lt)), pq = q();
+      if (DIRECT) {
+        if (base + pos < a.out_cap) {
+          a.out_pkg[base + pos] = a.out_base + a.p0 + pbase + pq;
+          a.out_adv[base + pos] = adv;
+        }
+      } else if (pos < uint32_t(MBW)) {
+        madv[pos] = adv;
+        mq[pos] = uint8_t(pq);
+      }
+    }
+    nm += uint32_t(__popcll(bal));
+  };
+  if constexpr (REC) {
+    static_assert(R16 == 3, "the rank-indexed windows are the hot-row sweep's");
+    for (uint32_t b0 = s0; b0 < s1; b0 += 64 * K) {
+      Row16 hrow[K];
+      uint64_t ph[K];
+      uint32_t pt[K], rd[K], rk[K];
+#pragma unroll
+      for (int k = 0; k < K; k++) rk[k] = map_rank(s, map, shift, min(b0 + k * 64 + lane, s1 - 1));
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+        rd[k] = min(b0 + k * 64 + lane, s1 - 1) + s.nz_rd[rk[k]];
+        ph[k] = hot.head[rk[k]];
+        pt[k] = hot.tail[rk[k]];
+      }
+#pragma unroll
+      for (int k = 0; k < K; k++) hrow[k] = a.db.rows16[rd[k]];
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+        bool slow;
+        bool m = row16_test_lex(ph[k], pt[k], hrow[k], slow);
+        if (slow) {  // rare
+          const uint32_t q = s.nz_q[rk[k]];
+          m = eval_row<FILT>(a, s, q, pbase + q, a.db.rows[rd[k]], rd[k]) != 0;
+        }
+        place(m && b0 + k * 64 + lane < s1, hrow[k].adv & ROW_ADV_MASK, [&] { return s.nz_q[rk[k]]; });
+      }
+    }
+    return nm;
+  }
   for (uint32_t b0 = s0; b0 < s1; b0 += 64 * K) {
     Row row[R16 == 3 ? 1 : K];
     Row16 hrow[R16 == 3 ? K : 1];
@@ -894,22 +948,8 @@ __device__ __forceinline__ uint32_t sweep_seg(const SweepArgs& a, const SweepSha
       } else {
         m = eval_row<FILT>(a, s, qq[k], pbase + qq[k], row[k], rid[k]) != 0;
       }
-      m = m && b0 + k * 64 + lane < s1;
-      const unsigned long long bal = __ballot(m);
-      if (m) {
-        const uint32_t pos = nm + uint32_t(__popcll(bal & lt));
-        const uint32_t adv = (R16 == 3 ? hrow[k].adv : row[R16 == 3 ? 0 : k].adv) & ROW_ADV_MASK;
-        if (DIRECT) {
-          if (base + pos < a.out_cap) {
-            a.out_pkg[base + pos] = a.out_base + a.p0 + pbase + qq[k];
-            a.out_adv[base + pos] = adv;
-          }
-        } else if (pos < uint32_t(MBW)) {
-          madv[pos] = adv;
-          mq[pos] = uint8_t(qq[k]);
-        }
-      }
-      nm += uint32_t(__popcll(bal));
+      place(m && b0 + k * 64 + lane < s1, (R16 == 3 ? hrow[k].adv : row[R16 == 3 ? 0 : k].adv) & ROW_ADV_MASK,
+            [&] { return qq[k]; });
     }
   }
   return nm;
@@ -929,7 +969,8 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, SweepShared<FILT>
   if constexpr (FILT < 2) s.k2[tid] = r.k2;
   s.kinfo[tid] = r.meta.z;
   s.koff[tid] = r.meta.w;
-  if constexpr (((SEG >> 2) & 3) == 3) {  // hot-row sweep: the package's window behind its key's prefix
+  constexpr bool kRec = (SEG & 16) != 0;  // the hot-row sweep with rank-indexed windows (sweep_seg REC)
+  if constexpr (((SEG >> 2) & 3) == 3 && !kRec) {  // hot-row sweep: the package's window behind its key's prefix
     const uint32_t ki = r.meta.z;
     uint64_t hh;
     uint32_t ht;
@@ -957,6 +998,15 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, SweepShared<FILT>
     s.nz_scan[nrank] = excl;
     s.nz_rd[nrank] = r.meta.x - excl;
     s.nz_q[nrank] = tid;
+    if constexpr (kRec) {
+      const uint32_t ki = r.meta.z;
+      uint64_t hh;
+      uint32_t ht;
+      row16_pkg_lex(r.k0, r.k1, r.k2, ki & KI_LEN, (ki >> KI_P_SHIFT) & KI_P_MASK, (ki >> KI_PFX_SHIFT) & KI_PFX_MASK,
+                    (ki & KI_VALID) != 0, hh, ht);
+      hot.head[nrank] = hh;
+      hot.tail[nrank] = ht;
+    }
   }
   if (tid == 0) s.nz_scan[nnz] = total;
   __syncthreads();
@@ -982,7 +1032,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, SweepShared<FILT>
     const uint32_t s0 = min(total, wave * seg), s1 = min(total, s0 + seg);
     uint32_t* madv_w = madv + wave * MBW;
     uint8_t* mq_w = mq + wave * MBW;
-    const uint32_t nmw = sweep_seg<K, MBW, FILT, false, R16>(a, s, madv_w, mq_w, map, nnz, total, s0, s1, lane, 0, hot);
+    const uint32_t nmw = sweep_seg<K, MBW, FILT, false, R16, kRec>(a, s, madv_w, mq_w, map, nnz, total, s0, s1, lane, 0, hot);
     if (lane == 0) s.wsum[0][wave] = nmw;  // the row-count scan is done with wsum[0]
     __syncthreads();
     uint32_t woff = 0, nm = 0;
@@ -1011,7 +1061,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, SweepShared<FILT>
         }
       }
     } else {
-      sweep_seg<K, MBW, FILT, true, R16>(a, s, madv_w, mq_w, map, nnz, total, s0, s1, lane, base, hot);  // rare
+      sweep_seg<K, MBW, FILT, true, R16, kRec>(a, s, madv_w, mq_w, map, nnz, total, s0, s1, lane, base, hot);  // rare
     }
     return;
   }
@@ -1180,7 +1230,8 @@ void launch_fused(uint32_t n_tiles, hipStream_t st, const FusedArgs& a) {
 // Table entry of variant (F, K, MB) for grammar set GM / row-filter level FILT
 // (match_variants.h: F = 0 split, 1-3 fused, 4 fused with per-wave sweep segments, 5 also
 // per-wave staging, 6 the same held at 6 waves, 7 per-wave staging + segments over the hot rows
-// (DB::rows16, dpkg-only), 11-15 and 25-26 fused measurement builds).
+// (DB::rows16, dpkg-only), 8 the same with rank-indexed windows and the one-compare pair test, 11-15
+// and 25-26 fused measurement builds).
 template <uint32_t GM, int FILT, int F, int K, int MB>
 constexpr FusedFn fused_entry() {
   if constexpr (F == 0) return nullptr;
@@ -1189,6 +1240,9 @@ constexpr FusedFn fused_entry() {
   else if constexpr (F == 6) return &launch_fused<GM, K, MB, FILT, 0, 6, 3>;
   else if constexpr (F == 7) {  // per-wave staging + segments over the 16-byte hot rows: dpkg-only batches
     if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | 12>;
+    else return nullptr;
+  } else if constexpr (F == 8) {  // the same with rank-indexed windows and the one-compare pair test (sweep_seg REC)
+    if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | 12 | 16>;
     else return nullptr;
   } else if constexpr (F == 25 || F == 26) {  // TVM_DIAG: 16-byte row loads, dpkg-only
     if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | (F == 25 ? 4 : 8)>;

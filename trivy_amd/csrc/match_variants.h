@@ -16,7 +16,8 @@
   X(6, 2, 2400, "fused_k2_m2400_wseg6") \
   X(6, 3, 2400, "fused_k3_m2400_wseg6") \
   X(7, 4, 2400, "fused_k4_m2400_wseg_r16") \
-  X(7, 8, 2400, "fused_k8_m2400_wseg_r16")
+  X(7, 8, 2400, "fused_k8_m2400_wseg_r16") \
+  X(8, 4, 2400, "fused_k4_m2400_wseg_rec_r16")
 
 // Measurement-only variants (wrong match lists by construction): built only with
 // `make DIAG=1` (-DTVM_DIAG), never reachable in the product library.
@@ -56,7 +57,10 @@ constexpr int kNumTuned = 0 TVM_MATCH_VARIANTS(TVM_VARIANT_COUNT_);
 // Since the 16-byte hot rows (DB::rows16): the same kernel sweeping them, K = 4 (C2 sweep,
 // profiles/row16/sweep_c2.txt: 0.3754 ms against 0.3836; K = 8 holds 115 VGPRs, 4 waves per SIMD
 // instead of 5: 0.4232 ms).  fused_k4_m2400_wseg stays in the list as its A/B partner.
-constexpr int kAutoVariant = 9;          // fused_k4_m2400_wseg_r16
+// Since the rank-indexed package windows and the one-compare pair test (sweep_seg REC; C2 sweep,
+// profiles/instr/sweep_c2.txt: 1.5 % under the parent's sweep, 193 fewer vector instructions per wave):
+// fused_k4_m2400_wseg_rec_r16; fused_k4_m2400_wseg_r16 stays as its A/B partner.
+constexpr int kAutoVariant = 11;         // fused_k4_m2400_wseg_rec_r16
 constexpr int kAutoVariantFiltered = 1;  // fused_k2_m2048
 // OS grammar sets with row filters (rpm / apk: no library rows): per-wave staging + segments
 // at 6 waves, K = 2 (round 5 sweep, profiles/r05/sweep_c5.txt: C5 2.317 -> 2.283 ms)

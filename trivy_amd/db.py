@@ -101,7 +101,8 @@ class DB:
         if n < 0:
             return None
         path, res = (ctypes.c_uint8 * max(n, 1))(), (ctypes.c_uint8 * max(n, 1))()
-        lib().tvm_row16_eval_host(self.h, bucket.encode(), name, len(name), version, len(version), path, res, n)
+        if lib().tvm_row16_eval_host(self.h, bucket.encode(), name, len(name), version, len(version), path, res, n) != n:
+            raise RuntimeError("row16: the two forms of the hot-row test disagree")  # -2 (capi.cpp)
         return [(int(path[i]), int(res[i])) for i in range(n)]
 
     def __del__(self):
