@@ -373,8 +373,34 @@ int tvm_batch_upload_into(tvm_engine* e, tvm_batch* b, void* pkg_dev, void* adv_
  * flags has TVM_PIPE_RAW, the batch travels in its transport form when it has one (every
  * name and version under 256 bytes, at most 255 platforms): each distinct name and each
  * distinct version string crosses the link once, packages carry references to them, and
- * the GPU rebuilds the batch's arrays chunk by chunk (one DMA per chunk). */
-enum { TVM_PIPE_RAW = 1, TVM_PIPE_ADV32 = 2 };
+ * the GPU rebuilds the batch's arrays chunk by chunk (one DMA per chunk).
+ *
+ * TVM_PIPE_RH_MERGE: every pass merges the findings of Red Hat packages per VulnerabilityID
+ * (redhat.go:146-187) chunk by chunk on the GPU, behind the chunk's match launch and ahead of
+ * its result move.  A pass then returns one entry per driver-reported vulnerability - a Red Hat
+ * package one per (package, VulnerabilityID), in VulnerabilityID order; packages of every other
+ * driver their lists unchanged - and the entries are record indices as tvm_vuln_set.rec defines
+ * them: the advisory index for every plain pair and for a Red Hat group of one member,
+ * n_adv_recs + k for the k-th group of several members.  tvm_pipeline_result,
+ * tvm_pipeline_result_raw and tvm_pipeline_vulns hand out exactly these indices.  The numbering
+ * k belongs to one pass (the groups take their numbers in the order their tiles finish); the
+ * pass leaves the groups' {first member, representative, members} in device memory, and
+ * tvm_pipeline_vulns fetches that list (16 bytes per group, 4 per member) and builds grp_recs
+ * from it on the host threads - no merge or export kernel, no second result move; with a
+ * filter set, the slots of groups the filter dropped stay in grp_recs as unreferenced records.
+ * *n_matches of tvm_pipeline_run and the overflow rule stay on the raw match count;
+ * tvm_pipeline_filter_stats is {raw, entries returned} (after the merge, and after the filter
+ * when one is set) and tvm_pipeline_stats[1] = 4 * packages + width * entries returned: the
+ * bytes of the pass itself, without the group and member lists tvm_pipeline_vulns fetches
+ * afterwards (C5 at 20M packages: 6.9 MB).
+ * Index width, decided here for a batch that holds Red Hat packages: 3 bytes when
+ * n_adv_recs + match_cap / 2 < 2^24 (a group of several members consumes at least two raw
+ * matches, so groups number at most match_cap / 2) and TVM_PIPE_ADV32 is not set, else 4.  A
+ * batch without Red Hat packages has no groups and keeps the rule without the flag (3 bytes
+ * when the DB has fewer than 2^24 advisories and TVM_PIPE_ADV32 is not set).  With the flag tvm_pipeline_set_filter accepts a batch
+ * with Red Hat packages.  For a batch without Red Hat packages the flag changes nothing.  A new
+ * tvm_pipeline_prepare without the flag returns to raw passes. */
+enum { TVM_PIPE_RAW = 1, TVM_PIPE_ADV32 = 2, TVM_PIPE_RH_MERGE = 4 };
 int tvm_pipeline_prepare(tvm_engine* e, tvm_batch* b, uint64_t match_cap, uint32_t chunk_packages, uint32_t flags,
                          char* err, size_t errlen);
 /* One pass; ms = wall time of the call.  TVM_EINVAL with *n_matches set when the matches do
@@ -511,7 +537,9 @@ typedef struct {
 int tvm_match_vulns(tvm_engine* e, tvm_batch* b, tvm_vuln_set* out, char* err, size_t errlen);
 /* The same from the last completed tvm_pipeline_run (TVM_EINVAL before one).  Batches without
  * Red Hat packages: the lists that pass left in pinned memory, no copy - the set is invalidated
- * by the next tvm_pipeline_prepare / tvm_pipeline_run / tvm_batch_free of the batch.  Batches
+ * by the next tvm_pipeline_prepare / tvm_pipeline_run / tvm_batch_free of the batch.  The same
+ * holds, lifetime rule included, for a pass prepared with TVM_PIPE_RH_MERGE: its lists are the
+ * set, and only grp_recs is built here (owned by the set).  Other batches
  * with Red Hat packages: the per-CVE merge (redhat.go:146-187) and the export run on the device
  * over the pass's match list (still in HBM), and the set owns its lists (valid until
  * tvm_vuln_set_free). */
@@ -668,11 +696,14 @@ int tvm_match_filter_time(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* o,
  * *n_matches stays the raw match count (and the pass still needs match_cap >= it), while
  * tvm_pipeline_result, tvm_pipeline_result_raw and tvm_pipeline_vulns return the kept lists
  * (n = the kept count) and tvm_pipeline_stats[1] counts the kept findings' bytes.
- * TVM_EINVAL: no prepared pipeline, a batch with Red Hat packages (redhat.go:146-187 takes a
- * merged group's Status and Severity from its first member, so the per-CVE merge must see the
- * unfiltered lists), or o->ignore / o->n_vex set (those need whole results: tvm_match_filter). */
+ * TVM_EINVAL: no prepared pipeline, a batch with Red Hat packages prepared without
+ * TVM_PIPE_RH_MERGE (redhat.go:146-187 takes a merged group's Status and Severity from its first
+ * member, so the per-CVE merge must see the unfiltered lists: with the flag it runs in the pass,
+ * ahead of the filter, and a group is tested by its first member's severity and status,
+ * StatusFixed when any member is fixed, vulnerability.go:65-66), or o->ignore / o->n_vex set (those need whole results: tvm_match_filter). */
 int tvm_pipeline_set_filter(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* o, char* err, size_t errlen);
-/* out = {raw matches, kept} of the last completed pass (equal without a filter). */
+/* out = {raw matches, entries returned} of the last completed pass (equal without a filter and
+ * without TVM_PIPE_RH_MERGE). */
 int tvm_pipeline_filter_stats(tvm_batch* b, uint64_t out[2]);
 
 #ifdef __cplusplus

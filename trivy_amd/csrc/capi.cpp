@@ -1645,6 +1645,8 @@ int tvm_match_filter_time(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* o,
 
 namespace {
 bool batch_has_redhat(const tvm_batch* b, const DB& db);
+bool ensure_rh_rank(tvm_engine* e, std::string& err);
+std::vector<uint8_t> rh_tile_flags(const HostBatch& hb, const DB& db, uint32_t n_tiles);
 
 // The advisory classes of the engine's current tables (prefilter.hip), built by the first
 // filtered pass after open / swap.  Callers hold the engine's lock (shared).
@@ -1659,7 +1661,7 @@ bool ensure_cls(tvm_engine* e, std::string& err) {
 int tvm_pipeline_prepare(tvm_engine* e, tvm_batch* b, uint64_t match_cap, uint32_t chunk_packages, uint32_t flags,
                          char* err, size_t errlen) {
   if (!e || !b || chunk_packages == 0 ||
-      (flags & ~uint32_t(TVM_PIPE_RAW | TVM_PIPE_ADV32)))
+      (flags & ~uint32_t(TVM_PIPE_RAW | TVM_PIPE_ADV32 | TVM_PIPE_RH_MERGE)))
     return TVM_EINVAL;
   std::shared_lock<std::shared_mutex> lk(e->mu);
   if (!bind(b, e)) {
@@ -1672,14 +1674,32 @@ int tvm_pipeline_prepare(tvm_engine* e, tvm_batch* b, uint64_t match_cap, uint32
   b->pipe_rh.forget_tiles();
   b->pipe_wide_for = ~0ull;
   std::string msg;
-  const bool packed = !(flags & TVM_PIPE_ADV32) && e->db->db.advs.size() < (1ull << 24);
-  if (!b->pipe->prepare(*e->eng, b->hb, match_cap, chunk_packages, !(flags & TVM_PIPE_RAW), packed, msg)) {
+  const DB& db = e->eng->db();
+  // once per batch, here: tvm_pipeline_vulns reads the answer.  The flag changes nothing for a
+  // batch without Red Hat packages: its pass enqueues what it always did
+  const bool merge = batch_has_redhat(b, db) && (flags & TVM_PIPE_RH_MERGE);
+  bool packed = !(flags & TVM_PIPE_ADV32) && e->db->db.advs.size() < (1ull << 24);
+  RhMergePrep rp;
+  if (merge) {
+    // the result holds record indices: an advisory, or n_adv_recs + k for the k-th group of
+    // several members, each of which holds at least two of the match_cap raw matches
+    packed = !(flags & TVM_PIPE_ADV32) && db.advs.size() + std::max<uint64_t>(match_cap, 1) / 2 < (1ull << 24);
+    (void)hipSetDevice(e->device);
+    if (!ensure_rh_rank(e, msg)) {
+      b->pipe.reset();
+      set_err(err, errlen, "tvm_pipeline_prepare: " + msg);
+      return TVM_EDEVICE;
+    }
+    rp.tile_rh = rh_tile_flags(b->hb, db, b->hb.n_tiles());
+    rp.n_adv_recs = uint32_t(db.advs.size());
+  }
+  if (!b->pipe->prepare(*e->eng, b->hb, match_cap, chunk_packages, !(flags & TVM_PIPE_RAW), packed, msg,
+                        merge ? &rp : nullptr)) {
     b->pipe.reset();
     set_err(err, errlen, msg);
     return TVM_EDEVICE;
   }
   b->pinned = true;  // the pipeline was sized for exactly these packages: no more adds
-  (void)batch_has_redhat(b, e->eng->db());  // once per batch, here: tvm_pipeline_vulns reads the answer
   return TVM_OK;
 }
 
@@ -1702,14 +1722,29 @@ int tvm_pipeline_run(tvm_engine* e, tvm_batch* b, uint64_t* n_matches, int64_t* 
     set_err(err, errlen, "tvm_pipeline_run: " + msg);
     return TVM_EDEVICE;
   }
-  const bool ok = b->pipe->run(*e->eng, b->hb, total, ep, bits, msg, e->cls, e->fill->dev().n_advs);
+  RhMergeRun rr;
+  if (b->pipe->rh_merge()) {
+    (void)hipSetDevice(e->device);
+    if (!ensure_rh_rank(e, msg)) {
+      set_err(err, errlen, "tvm_pipeline_run: " + msg);
+      return TVM_EDEVICE;
+    }
+    rr.rk = e->rh_rank;
+    rr.n_rk = uint32_t(e->eng->db().advs.size());
+    rr.plats = e->eng->device_plats();
+    rr.n_plats = uint32_t(e->eng->db().plat_info.size());
+  }
+  const bool ok = b->pipe->run(*e->eng, b->hb, total, ep, bits, msg, e->cls, e->fill->dev().n_advs,
+                               b->pipe->rh_merge() ? &rr : nullptr);
   const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (!ok) {
     set_err(err, errlen, msg);
     return TVM_EDEVICE;
   }
   if (bits) {
-    set_err(err, errlen, "match kernel internal error bits " + std::to_string(bits));
+    set_err(err, errlen, (bits & ERR_RH_ORDER)
+                             ? "tvm_pipeline_run: a Red Hat package's advisories are not grouped by VulnerabilityID"
+                             : "match kernel internal error bits " + std::to_string(bits));
     return TVM_EDEVICE;
   }
   b->pipe_total = total;
@@ -1747,11 +1782,11 @@ int tvm_pipeline_set_filter(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* 
                          "(tvm_match_filter); only the severity and status masks are tested in the pass");
     return TVM_EINVAL;
   }
-  if (batch_has_redhat(b, e->eng->db())) {
+  if (batch_has_redhat(b, e->eng->db()) && !b->pipe->rh_merge()) {
     // redhat.go:146-187: a merged group takes Status and Severity from its first member, so
-    // the merge has to see the unfiltered lists
+    // the merge has to see the unfiltered lists - it does when it runs in the pass, ahead of the filter
     set_err(err, errlen, "tvm_pipeline_set_filter: the batch holds Red Hat packages, whose per-CVE merge reads "
-                         "the unfiltered lists");
+                         "the unfiltered lists (prepare with TVM_PIPE_RH_MERGE to merge in the pass)");
     return TVM_EINVAL;
   }
   std::string msg;
@@ -2121,8 +2156,9 @@ const VulnTemplates& templates(tvm_db* d) {
 // merged Red Hat groups' records; a pipelined pass's set points into its result (no copy).
 struct VulnSetStore {
   VulnExport ex;
-  std::vector<tvm_vuln> gc;
-  std::vector<std::vector<const char*>> gvp;
+  std::unique_ptr<tvm_vuln[]> gc;  // the groups' records (n_gc)
+  size_t n_gc = 0;
+  std::vector<std::vector<const char*>> gvp;  // their unioned VendorIDs, one block per worker piece
 };
 
 bool batch_has_redhat(const tvm_batch* b, const DB& db) {
@@ -2156,18 +2192,76 @@ void set_out(tvm_db* d, VulnSetStore* st, const uint32_t* row_end, size_t n_pkgs
   out->n = n;
   out->adv_recs = t.c.data();
   out->n_adv_recs = t.c.size();
-  out->grp_recs = st->gc.data();
-  out->n_grp_recs = st->gc.size();
+  out->grp_recs = st->gc.get();
+  out->n_grp_recs = st->n_gc;
   out->priv = st;
 }
 
 
+// One merged Red Hat group as the record builder reads it: its first member, its representative
+// (the member whose FixedVersion the group reports) and its members, advisory indices in Get order.
+struct GroupView {
+  uint32_t base, best;
+  const uint32_t* mem;
+  uint32_t n_mem;
+};
+
+// The records of merged Red Hat groups (st.gc[k], k < n_groups) built on the host threads from
+// their members' own records - the first member's (ID, Status, Severity), the representative's
+// FixedVersion, and VendorIDs: the first member's own when it is the one fixed member, else the
+// sorted union of the fixed members' (ustrings.Unique; redhat.go:146-187) - as pointers into
+// those records.  view(k) = group k.
+template <class F>
+void build_group_records(const DB& db, const VulnTemplates& tp, size_t n_groups, F&& view, VulnSetStore& st) {
+  // 136 bytes a record and one VendorIDs list per merged group (C5: 285k groups, 39 MB): the
+  // records are left uninitialised here and every one is written below, so their pages are
+  // first touched on the worker threads, and a piece's lists share one block (a piece's groups
+  // point into it once it has stopped growing)
+  st.gc.reset(new tvm_vuln[n_groups]);
+  st.n_gc = n_groups;
+  std::mutex mu;
+  constexpr size_t kNoList = ~size_t(0);
+  pool_range_for(n_groups, 1 << 10, [&](size_t a, size_t z) {
+    std::vector<const char*> ids, block;
+    std::vector<size_t> at(z - a, kNoList);
+    for (size_t k = a; k < z; k++) {
+      const GroupView g = view(k);
+      const tvm_vuln& base = tp.c[g.base];
+      tvm_vuln& c = st.gc[k];
+      c = base;
+      const bool has_best = !db.advs[g.best].fixed.empty();
+      c.fixed_version = has_best ? tp.c[g.best].fixed_version : "";
+      uint32_t n_fixed = 0;
+      ids.clear();
+      for (uint32_t m = 0; m < g.n_mem; m++) {
+        const uint32_t adv = g.mem[m];
+        if (adv >= db.advs.size() || db.advs[adv].fixed.empty()) continue;
+        n_fixed++;
+        const tvm_vuln& mv = tp.c[adv];
+        ids.insert(ids.end(), mv.vendor_ids, mv.vendor_ids + mv.n_vendor_ids);
+      }
+      if (n_fixed == 1 && !db.advs[g.base].fixed.empty()) continue;  // the first member's list as it is
+      c.vendor_ids = nullptr;
+      c.n_vendor_ids = 0;
+      if (!n_fixed) continue;
+      std::sort(ids.begin(), ids.end(), [](const char* x, const char* y) { return std::strcmp(x, y) < 0; });
+      ids.erase(std::unique(ids.begin(), ids.end(), [](const char* x, const char* y) { return !std::strcmp(x, y); }),
+                ids.end());
+      if (ids.empty()) continue;
+      at[k - a] = block.size();
+      block.insert(block.end(), ids.begin(), ids.end());
+      c.n_vendor_ids = ids.size();
+    }
+    for (size_t k = a; k < z; k++)
+      if (at[k - a] != kNoList) st.gc[k].vendor_ids = block.data() + at[k - a];
+    std::lock_guard<std::mutex> g(mu);
+    st.gvp.push_back(std::move(block));  // a moved vector keeps its storage: the pointers stay valid
+  });
+}
+
 // The DetectedVulnerability set of a device match list `in` (raw, or Red Hat-merged): the
 // export's per-package record lists in pinned memory, and the records of the merged Red Hat
-// groups built on the host threads from their members' own records - the first member's (ID,
-// Status, Severity), the representative's FixedVersion, and VendorIDs: the first member's own
-// when it is the one fixed member, else the sorted union of the fixed members'
-// (ustrings.Unique; redhat.go:146-187) - as pointers into those records.
+// groups (build_group_records) from the export's group and member lists.
 bool export_set(tvm_engine* e, const ExportList& in, size_t n_pkgs, uint32_t first_pkg, tvm_vuln_set* out,
                 std::string& msg) {
   const DB& db = e->eng->db();
@@ -2175,40 +2269,11 @@ bool export_set(tvm_engine* e, const ExportList& in, size_t n_pkgs, uint32_t fir
   auto st = std::make_unique<VulnSetStore>();
   if (!export_vulns(e->device, e->eng->stream(), in, uint32_t(db.advs.size()), st->ex, msg)) return false;
   const VulnExport& ex = st->ex;
-  if (ex.n_groups) {
-    st->gc.resize(ex.n_groups);
-    st->gvp.resize(ex.n_groups);
-    pool_range_for(ex.n_groups, 1 << 10, [&](size_t a, size_t z) {
-      std::vector<const char*> ids;
-      for (size_t k = a; k < z; k++) {
-        const uint4 g = ex.groups[k];
-        const tvm_vuln& base = tp.c[g.z];
-        tvm_vuln& c = st->gc[k];
-        c = base;
-        const bool has_best = !db.advs[g.w].fixed.empty();
-        c.fixed_version = has_best ? tp.c[g.w].fixed_version : "";
-        uint32_t n_fixed = 0;
-        ids.clear();
-        for (uint32_t m = ex.moff[k]; m < ex.moff[k + 1]; m++) {
-          const uint32_t adv = ex.members[m];
-          if (adv >= db.advs.size() || db.advs[adv].fixed.empty()) continue;
-          n_fixed++;
-          const tvm_vuln& mv = tp.c[adv];
-          ids.insert(ids.end(), mv.vendor_ids, mv.vendor_ids + mv.n_vendor_ids);
-        }
-        if (n_fixed == 1 && !db.advs[g.z].fixed.empty()) continue;  // the first member's list as it is
-        c.vendor_ids = nullptr;
-        c.n_vendor_ids = 0;
-        if (!n_fixed) continue;
-        std::sort(ids.begin(), ids.end(), [](const char* x, const char* y) { return std::strcmp(x, y) < 0; });
-        ids.erase(std::unique(ids.begin(), ids.end(), [](const char* x, const char* y) { return !std::strcmp(x, y); }),
-                  ids.end());
-        st->gvp[k] = ids;
-        c.vendor_ids = st->gvp[k].empty() ? nullptr : st->gvp[k].data();
-        c.n_vendor_ids = st->gvp[k].size();
-      }
-    });
-  }
+  if (ex.n_groups)
+    build_group_records(db, tp, ex.n_groups, [&](size_t k) {
+      const uint4 g = ex.groups[k];
+      return GroupView{g.z, g.w, ex.members.data() + ex.moff[k], ex.moff[k + 1] - ex.moff[k]};
+    }, *st);
   const VulnSetStore* sp = st.get();
   set_out(e->db, st.release(), sp->ex.row_end_h, n_pkgs, first_pkg, sp->ex.rec_h, sp->ex.width, sp->ex.n, out);
   return true;
@@ -2286,9 +2351,47 @@ int tvm_pipeline_vulns(tvm_engine* e, tvm_batch* b, tvm_vuln_set* out, char* err
     return TVM_EINVAL;
   }
   const DB& db = e->eng->db();
-  if (!batch_has_redhat(b, db)) {  // the lists the pass left in pinned memory ARE the set (no copy)
-    templates(e->db);
+  // the lists the pass left in pinned memory ARE the set (no copy): a batch without Red Hat
+  // packages, or a pass that merged them chunk by chunk (TVM_PIPE_RH_MERGE; rhmerge.hip)
+  if (!batch_has_redhat(b, db) || b->pipe->rh_merge()) {
+    const VulnTemplates& tp = templates(e->db);
     auto st = std::make_unique<VulnSetStore>();
+    const Pipeline& P = *b->pipe;
+    if (P.rh_merge() && P.n_groups()) {
+      // the pass's group list (HBM) -> the groups' records, on the host threads
+      // (pinned blocks from the cache: a pageable destination halves the copy's rate)
+      const size_t ng = P.n_groups(), nm = P.n_members(), b_g = (ng * sizeof(uint4) + 15) & ~size_t(15);
+      std::string msg;
+      struct Pinned {
+        void* p;
+        ~Pinned() { pool_host_put(p); }
+      } buf{pool_host_get(b_g + std::max<size_t>(nm, 1) * 4, "hipHostMalloc(merged groups)", msg)};
+      const uint4* groups = static_cast<const uint4*>(buf.p);
+      const uint32_t* members = reinterpret_cast<const uint32_t*>(static_cast<const char*>(buf.p) + b_g);
+      (void)hipSetDevice(e->device);
+      hipStream_t hs = e->eng->stream();
+      if (!buf.p || hipMemcpyAsync(buf.p, P.groups_dev(), ng * sizeof(uint4), hipMemcpyDeviceToHost, hs) != hipSuccess ||
+          (nm && hipMemcpyAsync(static_cast<char*>(buf.p) + b_g, P.members_dev(), nm * 4, hipMemcpyDeviceToHost, hs) !=
+                     hipSuccess) ||
+          hipStreamSynchronize(hs) != hipSuccess) {
+        set_err(err, errlen, "tvm_pipeline_vulns: fetching the merged groups failed" + (msg.empty() ? "" : ": " + msg));
+        return TVM_EDEVICE;
+      }
+      const uint32_t n_adv = uint32_t(db.advs.size());
+      std::atomic<bool> bad{false};
+      pool_range_for(ng, 1 << 14, [&](size_t a, size_t z) {  // {first member, representative, member offset, member count}
+        for (size_t k = a; k < z; k++)
+          if (groups[k].x >= n_adv || groups[k].y >= n_adv || uint64_t(groups[k].z) + groups[k].w > nm) bad = true;
+      });
+      if (bad) {
+        set_err(err, errlen, "tvm_pipeline_vulns: the pass's group list is inconsistent");
+        return TVM_EDEVICE;
+      }
+      build_group_records(db, tp, ng, [&](size_t k) {
+        const uint4 g = groups[k];
+        return GroupView{g.x, g.y, members + g.z, g.w};
+      }, *st);
+    }
     set_out(e->db, st.release(), b->pipe->row_end(), b->hb.pk.size(), b->pkg_base,
             reinterpret_cast<const uint8_t*>(b->pipe->adv()), b->pipe->packed() ? 3u : 4u, b->pipe_kept, out);
     return TVM_OK;

@@ -50,6 +50,49 @@ class FillEngine;
 // kernel over the identity list, narrowed to 16 bits.  Synchronises `st`.  nullptr + err on failure.
 uint16_t* build_class_table(FillEngine& fill, hipStream_t st, std::string& err);
 
+// The Red Hat per-CVE merge inside the pipelined pass (rhmerge.hip; redhat.go:146-187): one
+// chunk's match segments compacted in place to one entry per driver-reported vulnerability,
+// ahead of the chunk's result move.  A Red Hat package's members of one VulnerabilityID become
+// one entry whose adv column holds its record index (tvm_vuln_set.rec): the advisory for a
+// group of one member, n_adv_recs + k for the k-th group of several, which the kernel writes to
+// groups[k] = {first member, representative, member offset, member count} with its members
+// (advisory indices, Get order) at members[offset ..).  With f.cls set the severity / status
+// filter is applied to every entry on the way (a group: its first member's class, StatusFixed
+// when any member is fixed).
+struct RhMergeArgs {
+  PrefilterArgs f;  // dir / pkg / adv / t0 / t1 / cap / ctl; cls and the masks when `filter`
+  uint32_t filter = 0;
+  const uint8_t* tile_rh = nullptr;  // per tile: 1 = it holds Red Hat packages
+  const uint2* pk = nullptr;         // the batch's package words {platform, lengths}
+  const PlatInfo* plats = nullptr;
+  uint32_t n_plats = 0;
+  uint32_t n = 0;                    // packages in the batch
+  uint32_t pkg_base = 0;             // carried by the match list's package indices
+  const uint2* rk = nullptr;         // per advisory {VulnerabilityID rank, fixed-version rank (RH_NONE = unfixed)}
+  uint32_t n_rk = 0;
+  uint32_t n_adv_recs = 0;
+  uint4* groups = nullptr;
+  uint32_t* members = nullptr;
+  uint64_t grp_cap = 0, mem_cap = 0;  // entries of groups / members
+};
+// Control-block words of a merging pass: groups reserved << 32 | members reserved (one 64-bit
+// add per tile that has groups of several members), and the matches the merge removed from an
+// unfiltered pass (whose tiles without Red Hat packages are not visited: kept = raw - removed).
+constexpr int kCtlGroups = 5;
+constexpr int kCtlMerged = 6;
+void launch_rhmerge(hipStream_t st, const RhMergeArgs& a);
+// What prepare() needs to merge in the pass, and what each run() reads (engine-owned tables).
+struct RhMergePrep {
+  std::vector<uint8_t> tile_rh;  // per tile of the batch: 1 = it holds Red Hat packages
+  uint32_t n_adv_recs = 0;
+};
+struct RhMergeRun {
+  const uint2* rk = nullptr;
+  uint32_t n_rk = 0;
+  const PlatInfo* plats = nullptr;
+  uint32_t n_plats = 0;
+};
+
 
 // One batch's pipeline state.  prepare() builds the batch's pinned transport form (or a
 // pinned copy of its raw arrays), sizes the device batch, the match buffers and the pinned result buffers; run() then
@@ -58,7 +101,9 @@ uint16_t* build_class_table(FillEngine& fill, hipStream_t st, std::string& err);
 //   kernel stream  (after chunk c's upload) one match launch whose first workgroups turn
 //                  chunk c-1's match segments into the pinned host CSR (engine.h
 //                  copy_out_tiles: 16-byte kernel stores, the link's other direction) while
-//                  the rest match chunk c;
+//                  the rest match chunk c; behind it, when a filter is set or the pass merges
+//                  Red Hat findings, one launch that compacts chunk c's segments in place
+//                  (prefilter.hip / rhmerge.hip), so the move ships only what is returned;
 //   row-end stream DMA of chunk c-1's row ends (left in HBM by that result move) to the host;
 // so chunk c+1's upload and chunk c-1's result move run under chunk c's matching, and the
 // host waits once, at the end.  (Measured alternatives, DESIGN.md §7: a DMA device-to-host
@@ -70,12 +115,21 @@ class Pipeline {
   // transport: send the batch in its transport form when it has one (see build_wire)
   // packed: the result's advisory indices travel as 3 bytes each (the DB has < 2^24)
   bool prepare(Engine& eng, const HostBatch& hb, uint64_t match_cap, uint32_t chunk_packages, bool transport,
-               bool packed, std::string& err);
+               bool packed, std::string& err, const RhMergePrep* rh = nullptr);
   // One pass.  total = matches (> match_cap: nothing valid, re-prepare with a larger cap);
   // err_pkg = first poisoned package or -1.
   // cls / n_cls: the engine's advisory class table (prefilter.hip), read when a filter is set
+  // rh: the Red Hat rank table and the platforms, read when the pass merges (rh_merge())
   bool run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& err_pkg, uint64_t& err_bits, std::string& err,
-           const uint16_t* cls = nullptr, uint32_t n_cls = 0);
+           const uint16_t* cls = nullptr, uint32_t n_cls = 0, const RhMergeRun* rh = nullptr);
+  // prepare() was given the batch's Red Hat tiles: every pass merges each chunk's Red Hat
+  // findings per VulnerabilityID behind its match launch (rhmerge.hip), so the result holds
+  // record indices and the group list below describes the records of the merged groups
+  bool rh_merge() const { return rh_mode_; }
+  uint32_t n_groups() const { return n_groups_; }    // the last pass's group slots (dropped groups' slots are empty)
+  uint32_t n_members() const { return n_members_; }
+  const uint4* groups_dev() const { return groups_d_; }
+  const uint32_t* members_dev() const { return members_d_; }
   // The following passes return only the findings of these severities whose status is not
   // ignored (tested per chunk on the GPU, before the result move); cleared by clear_filter().
   // Without a filter a pass enqueues exactly what it did before filters existed.
@@ -145,6 +199,13 @@ class Pipeline {
   bool filter_ = false;
   uint32_t sev_mask_ = 0, status_mask_ = 0;
   uint64_t kept_ = 0;
+  // the merge in the pass (rh_merge()): the Red Hat tiles, the group and member lists (HBM)
+  bool rh_mode_ = false;
+  uint8_t* tile_rh_d_ = nullptr;
+  uint4* groups_d_ = nullptr;
+  uint32_t* members_d_ = nullptr;
+  uint64_t grp_cap_ = 0;
+  uint32_t n_adv_recs_ = 0, n_groups_ = 0, n_members_ = 0;
   bool packed_ = false;  // no Engine pointer: the batch may outlive a hot swap (the C-ABI checks the generation)
 };
 

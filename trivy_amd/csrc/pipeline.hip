@@ -211,8 +211,14 @@ void Pipeline::release() {
   Engine::free_batch(dev_, db_, true);
   Engine::free_matches(dev_, m_, true);
   for (void* p : {static_cast<void*>(chunk_base_d_), static_cast<void*>(wire_d_), static_cast<void*>(ptab_d_),
-                  static_cast<void*>(row_end_d_)})
+                  static_cast<void*>(row_end_d_), static_cast<void*>(tile_rh_d_), static_cast<void*>(groups_d_),
+                  static_cast<void*>(members_d_)})
     pool_device_put(dev_, p);
+  tile_rh_d_ = nullptr;
+  groups_d_ = nullptr;
+  members_d_ = nullptr;
+  rh_mode_ = false;
+  n_groups_ = n_members_ = 0;
   for (void* p : {static_cast<void*>(wire_h_), static_cast<void*>(raw_h_), static_cast<void*>(adv_h_),
                   static_cast<void*>(row_end_h_), static_cast<void*>(ctl_h_)})
     pool_host_put(p);
@@ -240,7 +246,7 @@ void Pipeline::release() {
 }
 
 bool Pipeline::prepare(Engine& eng, const HostBatch& hb, uint64_t match_cap, uint32_t chunk_packages, bool transport,
-                       bool packed, std::string& err) {
+                       bool packed, std::string& err, const RhMergePrep* rh) {
   release();
   const auto start = std::chrono::steady_clock::now();
   dev_ = eng.device();
@@ -322,15 +328,36 @@ bool Pipeline::prepare(Engine& eng, const HostBatch& hb, uint64_t match_cap, uin
   row_end_d_ = static_cast<uint32_t*>(p);
   if (!(p = pool_host_get(64, "hipHostMalloc(ctl)", err))) return false;
   ctl_h_ = static_cast<unsigned long long*>(p);
+  if (rh) {
+    // the merge in the pass: the Red Hat tiles (uploaded once, here) and the group and member
+    // lists - a group of several members holds at least two raw matches, a member is one
+    if (rh->tile_rh.size() != n_tiles) {
+      err = "pipeline: the Red Hat tile flags do not cover the batch";
+      return false;
+    }
+    grp_cap_ = cap_ / 2;
+    n_adv_recs_ = rh->n_adv_recs;
+    if (!(p = pool_device_get(dev_, std::max<size_t>(n_tiles, 1), "hipMalloc(red hat tiles)", err))) return false;
+    tile_rh_d_ = static_cast<uint8_t*>(p);
+    if (n_tiles && !ok(hipMemcpy(tile_rh_d_, rh->tile_rh.data(), n_tiles, hipMemcpyHostToDevice), "H2D red hat tiles", err))
+      return false;
+    if (!(p = pool_device_get(dev_, std::max<size_t>(grp_cap_, 1) * sizeof(uint4), "hipMalloc(merge groups)", err)))
+      return false;
+    groups_d_ = static_cast<uint4*>(p);
+    if (!(p = pool_device_get(dev_, cap_ * 4, "hipMalloc(merge members)", err))) return false;
+    members_d_ = static_cast<uint32_t*>(p);
+    rh_mode_ = true;
+  }
   prepared_ = true;
   prepare_us_ = uint64_t(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - start).count());
   return true;
 }
 
 bool Pipeline::run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& err_pkg, uint64_t& err_bits,
-                   std::string& err, const uint16_t* cls, uint32_t n_cls) {
+                   std::string& err, const uint16_t* cls, uint32_t n_cls, const RhMergeRun* rh) {
   total = 0;
   kept_ = 0;
+  n_groups_ = n_members_ = 0;
   err_pkg = -1;
   err_bits = 0;
   h2d_ = d2h_ = 0;
@@ -340,6 +367,10 @@ bool Pipeline::run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& e
   }
   if (filter_ && !cls) {
     err = "pipeline: a filter is set but the advisory class table is missing";
+    return false;
+  }
+  if (rh_mode_ && !(rh && rh->rk && rh->plats)) {
+    err = "pipeline: the pass merges Red Hat findings but the rank table is missing";
     return false;
   }
   (void)hipSetDevice(dev_);
@@ -443,9 +474,10 @@ bool Pipeline::run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& e
     const CopyOutArgs prev_co = prev >= 0 ? copy_args(uint32_t(prev)) : CopyOutArgs{};
     if (!eng.launch_tiles(db_, m_, t0, t1, s_k_, s_k_, nullptr, err, prev >= 0 ? &prev_co : nullptr)) return false;
     if (prev >= 0 && !rowend_up(uint32_t(prev))) return false;
-    if (filter_) {
-      // chunk c's segments are compacted to the findings that pass, behind its match launch and
-      // ahead of whatever moves its result out (chunk c + 1's launch, or the last copy-out below)
+    if (filter_ || rh_mode_) {
+      // chunk c's segments are compacted to the findings that pass (and, merging, to one entry per
+      // Red Hat vulnerability), behind its match launch and ahead of whatever moves its result
+      // out (chunk c + 1's launch, or the last copy-out below)
       PrefilterArgs pa;
       pa.dir = m_.dir;
       pa.pkg = m_.pkg;
@@ -458,7 +490,27 @@ bool Pipeline::run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& e
       pa.t1 = t1;
       pa.cap = cap_;
       pa.ctl = m_.ctl;
-      launch_prefilter(s_k_, pa);
+      if (rh_mode_) {
+        RhMergeArgs ra;
+        ra.f = pa;
+        ra.filter = filter_ ? 1u : 0u;
+        ra.tile_rh = tile_rh_d_;
+        ra.pk = db_.pk;
+        ra.plats = rh->plats;
+        ra.n_plats = rh->n_plats;
+        ra.n = n;
+        ra.pkg_base = db_.pkg_base;
+        ra.rk = rh->rk;
+        ra.n_rk = rh->n_rk;
+        ra.n_adv_recs = n_adv_recs_;
+        ra.groups = groups_d_;
+        ra.members = members_d_;
+        ra.grp_cap = grp_cap_;
+        ra.mem_cap = cap_;
+        launch_rhmerge(s_k_, ra);
+      } else {
+        launch_prefilter(s_k_, pa);
+      }
       if (!ok(hipGetLastError(), "prefilter kernel launch", err)) return false;
     }
     if (trace) std::fprintf(stderr, "pipe c%u match %.1f us\n", c, us());
@@ -475,7 +527,12 @@ bool Pipeline::run(Engine& eng, const HostBatch& hb, uint64_t& total, int64_t& e
   if (trace) std::fprintf(stderr, "pipe done %.1f us\n", us());
   // the overflow rule stays on the raw count (the match buffer holds raw matches); the result
   // and its link bytes are the kept findings
-  kept_ = filter_ ? ctl_h_[kCtlKept] : ctl_h_[0];
+  // (an unfiltered merging pass visits the Red Hat tiles only: kept = raw - what the merge removed)
+  kept_ = filter_ ? ctl_h_[kCtlKept] : ctl_h_[0] - (rh_mode_ ? ctl_h_[kCtlMerged] : 0);
+  if (rh_mode_) {
+    n_groups_ = uint32_t(ctl_h_[kCtlGroups] >> 32);
+    n_members_ = uint32_t(ctl_h_[kCtlGroups]);
+  }
   d2h_ = uint64_t(n) * 4 + std::min<uint64_t>(kept_, cap_) * (packed_ ? 3 : 4);
   total = ctl_h_[0];
   err_pkg = ctl_h_[1] ? int64_t(n - ctl_h_[1]) : -1;
