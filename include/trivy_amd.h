@@ -335,6 +335,13 @@ int tvm_deb_fast_key_host(const char* s, size_t n, uint32_t shift, uint8_t* out,
  * the lane stride) is written in place, so a test that pre-fills it sees every byte the
  * builder touched.  Returns as tvm_deb_fast_key_host (the length also for kb[0, len)). */
 int tvm_deb_fast_key_slot_host(const char* s, size_t n, uint32_t shift, uint8_t* kb, size_t kb_len);
+/* The balanced match kernel's encoder work list (verkey.h enc_bal_*), host-side for tests: the
+ * number of buckets; the bucket of a version of version_len bytes; and work item -> (bucket,
+ * index in the bucket's region) given the buckets' entry counts (counts[0 .. buckets)): 1, or 0
+ * when the item lies past the end of the list, -1 on a null argument. */
+int tvm_enc_bal_buckets_host(void);
+int tvm_enc_bal_bucket_host(uint32_t version_len);
+int tvm_enc_bal_item_host(const uint32_t* counts, uint32_t item, uint32_t* bucket, uint32_t* index);
 /* Host-side compare.IsVulnerable through the load-time interval compiler (tests): 1/0, -1
  * when the advisory JSON does not decode.  Maven: the rows the product builds - intervals for
  * an advisory whose bounds are all numeric, else the pairwise program - so it mirrors the

@@ -236,6 +236,10 @@ _SIG = [
                                              ctypes.c_size_t]),
     ("tvm_deb_fast_key_slot_host", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,
                                                   ctypes.c_size_t]),
+    ("tvm_enc_bal_buckets_host", ctypes.c_int, []),
+    ("tvm_enc_bal_bucket_host", ctypes.c_int, [ctypes.c_uint32]),
+    ("tvm_enc_bal_item_host", ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
+                                             ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("tvm_db_advisory_vuln_id", ctypes.c_char_p, [_P, ctypes.c_uint32]),
     ("tvm_version_class", ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_lib_is_vulnerable_host", ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,

@@ -1168,6 +1168,17 @@ int tvm_deb_fast_key_slot_host(const char* s, size_t n, uint32_t shift, uint8_t*
   return st == FAST_INVALID ? -1 : st == FAST_FALLBACK ? -2 : int(len);
 }
 
+int tvm_enc_bal_buckets_host(void) { return int(kEncBuckets); }
+int tvm_enc_bal_bucket_host(uint32_t version_len) { return int(enc_bal_bucket(version_len)); }
+int tvm_enc_bal_item_host(const uint32_t* counts, uint32_t item, uint32_t* bucket, uint32_t* index) {
+  if (!counts || !bucket || !index) return -1;
+  uint32_t b = 0, i = 0;
+  if (!enc_bal_item(counts, item, b, i)) return 0;
+  *bucket = b;
+  *index = i;
+  return 1;
+}
+
 int tvm_lib_is_vulnerable_host(int grammar, const char* ver, size_t ver_len, const char* advisory_json,
                                size_t json_len) {
   Advisory a;

@@ -247,12 +247,23 @@ __device__ __forceinline__ bool fp_chain(const ProbeArgs& a, uint64_t h, uint64_
 #endif
 }
 
+// What the balanced kernel (fused_kernel, SEG bit 5) has of a package before probe_one runs: the
+// name's hash, the fingerprint walk's outcome and the slot heads, and deb_fast_key's outcome and key
+// length, with the key already in the lane's LDS slot (PRE = 2).
+struct ProbePre {
+  uint64_t h, start;
+  uint4 q0, q0n;
+  bool found, has_q0n;
+  uint32_t fast_st, fast_kl;
+};
+
 // One package: encode, hash, probe.  P = uint32_t in the LDS or global address space of s.
 // kb / tab: the lane's LDS key buffer and the dpkg code table (nullptr: generic encoder only).
-template <uint32_t GM, class P, int DIAG = 0>
+template <uint32_t GM, class P, int DIAG = 0, int PRE = 0>
 __device__ __forceinline__ void probe_one(const ProbeArgs& a, uint32_t p, uint32_t plat, uint32_t nlen, uint32_t vlen,
                                           const uint8_t* name, const uint8_t* ver, uint64_t vglob, PkgRec& r,
-                                          uint8_t* kb = nullptr, const uint8_t* tab = nullptr) {
+                                          uint8_t* kb = nullptr, const uint8_t* tab = nullptr,
+                                          const ProbePre* pre = nullptr) {
   const PlatInfo pi = a.db.plats[plat];
   // the hash and the fingerprint walk come before the encoder; the dpkg-only kernels load the
   // slot heads before it too, the other grammar sets after it (their encoders' registers: held
@@ -262,7 +273,15 @@ __device__ __forceinline__ void probe_one(const ProbeArgs& a, uint32_t p, uint32
   bool found = false;
   uint4 q0 = make_uint4(0, 0, 0, 0), q0n = q0;
   bool has_q0n = false;
-  if (!(DIAG & 2)) {
+  if constexpr (PRE != 0) {
+    static_assert(GM == GM_DEB && DIAG == 0, "the balanced kernel is dpkg-only");
+    h = pre->h;
+    start = pre->start;
+    found = pre->found;
+    q0 = pre->q0;
+    q0n = pre->q0n;
+    has_q0n = pre->has_q0n;
+  } else if (!(DIAG & 2)) {
     h = name_hash<P>(plat, name, nlen);
     found = fp_chain(a, h, start);
   }
@@ -278,10 +297,16 @@ __device__ __forceinline__ void probe_one(const ProbeArgs& a, uint32_t p, uint32
       if (has_q0n) q0n = slot_head(a, start + 1);
     }
   };
-  if constexpr (kPre) heads();
+  if constexpr (kPre && PRE == 0) heads();
   if (!(DIAG & 1) && kb && ((GM >> CMP_DEB) & 1u) && pi.cmp == CMP_DEB) {
-    uint32_t kl = 0;
-    const uint32_t st = deb_fast_key(ver, vlen, kb, tab, kl);
+    uint32_t kl = 0, st;
+    // DIAG bit 3 (measurement only): the encoder sees at most 12 version bytes, 3 dword trips
+    if constexpr (PRE == 2) {
+      st = pre->fast_st;
+      kl = pre->fast_kl;
+    } else {
+      st = deb_fast_key(ver, (DIAG & 8) ? min(vlen, 12u) : vlen, kb, tab, kl);
+    }
     if (st != FAST_FALLBACK) {
       const bool valid = st == FAST_OK;
       const uint32_t* kw = reinterpret_cast<const uint32_t*>(kb);
@@ -1114,7 +1139,8 @@ __global__ __launch_bounds__(kTile) void sweep_kernel(SweepArgs a) {
 // Probe and sweep of one tile in one workgroup (the record stays in registers/LDS): tiles
 // of one CU sit in different phases, so one tile's probe latency overlaps another's sweep.
 // DIAG (measurement only, wrong match lists by construction; "diag_*" variants): bit 0 skips
-// the version encoder, bit 1 the index probe, bit 2 the sweep.
+// the version encoder, bit 1 the index probe, bit 2 the sweep, bit 3 cuts the fast encoder's input
+// to 12 bytes (probe_one).
 // STG: LDS bytes for the tile's string window (smaller: more tiles resident per CU, more
 // windows read from global memory instead).
 // MOVE: the launch carries the previous pipeline chunk's result move (fa.n_copy workgroups).
@@ -1132,9 +1158,23 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
     SweepShared<FILT> s;
     uint8_t map[kMapCap];
   };
+  // kBal (SEG bit 5, dpkg-only, per-wave staging): the tile's encoder work list.  Before the code
+  // table's barrier every lane hashes its name and walks the fingerprint chain; a lane whose name the
+  // index may hold enters its package in the list of its version's dword count (enc_bal_bucket).
+  // After the barrier lane i of the tile encodes work item i (enc_bal_item: longest bucket first)
+  // into that package's key slot, leaving deb_fast_key's outcome and the key length in slot bytes
+  // 40..43, which the encoder never writes; waves past the end of the list do nothing.  One more
+  // barrier, and every lane goes on with its own package's slot (probe_one PRE = 2).  A package
+  // whose name is absent gets no key and no rows.
+  constexpr bool kBal = (SEG & 32) != 0;
+  static_assert(!kBal || (GM == GM_DEB && (SEG & 2) && DIAG == 0), "encoder balance: dpkg-only, per-wave staging");
   struct ProbePart {
     uint32_t kbuf[kTile * kFastKeyStride / 4];
     uint8_t tab[128];
+    uint32_t bal_cnt[kBal ? kEncBuckets : 1];    // entries per bucket
+    uint32_t bal_mixed;                          // a wave's window is not staged: the tile runs lane per package
+    uint32_t bal_ver[kBal ? kTile : 1];          // per tile package: its version's byte offset in buf | length << 16
+    uint8_t bal_list[kBal ? kEncBuckets * kTile : 1];  // per bucket: the tile packages entered, in arrival order
   };
   static_assert(sizeof(ProbePart) <= sizeof(SweepPart), "the probe's LDS fits in the sweep's");
   __shared__ union {
@@ -1164,18 +1204,52 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
   constexpr bool kWaveStage = (SEG & 2) != 0;
   const uint32_t g = t * kGroupsPerTile + (kWaveStage ? (tid >> 6) : 0u);  // the window's first group
   const uint64_t w0 = a.tile_off[g], w1 = a.tile_off[kWaveStage ? g + 1 : (t + 1) * kGroupsPerTile];  // before the scan's barriers
+  if constexpr (kBal) {  // the list's counters, zero before any wave enters a package: under the loads above
+    if (tid < kEncBuckets) u.pr.bal_cnt[tid] = 0;
+    if (tid == kEncBuckets) u.pr.bal_mixed = 0;
+    __syncthreads();
+  }
   const uint32_t nlen = d.y & 0xFFFFu, vlen = d.y >> 16;
   uint32_t off = 0;
   uint4* sbuf = buf;  // this lane's staging window
   const uint64_t base16 = w0 & ~uint64_t(15);
   bool staged;
+  const bool own = p < a.n && d.x < a.db.n_plats;
+  ProbePre pre;  // kBal
+  pre.h = pre.start = 0;
+  pre.q0 = pre.q0n = make_uint4(0, 0, 0, 0);
+  pre.found = pre.has_q0n = false;
+  pre.fast_st = pre.fast_kl = 0;
+  bool listed = false;
   if constexpr (kWaveStage) {
     off = wave_exscan(nlen + vlen, tid & 63);
     sbuf = buf + (tid >> 6) * (STG / 4 / 16 + 2);
     staged = w1 - base16 <= STG / 4;
     if (staged) stage_window_wave<STG>(sbuf, a.arena + base16, uint32_t((w1 - base16 + 15) / 16), tid & 63);
     if (tid < 128) u.pr.tab[tid] = deb_fast_code(tid);
-    __syncthreads();  // the code table (one wave's LDS traffic alone is ordered)
+    if constexpr (kBal) {
+      if (!staged) {
+        if ((tid & 63) == 0) u.pr.bal_mixed = 1;
+      } else if (own) {
+        const uint32_t noff = uint32_t(reinterpret_cast<const uint8_t*>(sbuf) - reinterpret_cast<const uint8_t*>(buf)) +
+                              uint32_t(w0 - base16) + off;
+        pre.h = name_hash<uint32_t>(d.x, reinterpret_cast<const uint8_t*>(buf) + noff, nlen);
+        pre.found = fp_chain(a, pre.h, pre.start);
+        if (pre.found) {  // the slot heads, ahead of the encoder (probe_one heads)
+          pre.q0 = slot_head(a, pre.start);
+          pre.has_q0n = !(pre.start & 1);
+          if (pre.has_q0n) pre.q0n = slot_head(a, pre.start + 1);
+          listed = a.db.plats[d.x].cmp == CMP_DEB;
+          if (listed) {
+            const uint32_t b = enc_bal_bucket(vlen);
+            const uint32_t rank = atomicAdd(&u.pr.bal_cnt[b], 1u);  // < kTile: a lane enters at most once
+            u.pr.bal_list[b * kTile + rank] = uint8_t(tid);
+            u.pr.bal_ver[tid] = (noff + nlen) | (vlen << 16);
+          }
+        }
+      }
+    }
+    __syncthreads();  // the code table (one wave's LDS traffic alone is ordered) and the work list
   } else {
     block_exscan<kTile>(s.wsum[0], nlen + vlen, tid, off);
     staged = w1 - base16 <= STG;
@@ -1186,11 +1260,47 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
   PkgRec r;
   r.meta = make_uint4(0, 0, 0, 0);
   r.k0 = r.k1 = r.k2 = 0;
-  if (p < a.n && d.x < a.db.n_plats) {
+  if constexpr (kBal) {
+    uint8_t* const kbytes = reinterpret_cast<uint8_t*>(u.pr.kbuf);
+    const uint8_t* sb = reinterpret_cast<const uint8_t*>(sbuf) + uint32_t(w0 - base16) + off;
+    const bool packed = u.pr.bal_mixed == 0;  // uniform: every wave's window is staged
+    if (packed) {
+      uint32_t cnt[kEncBuckets];
+#pragma unroll
+      for (uint32_t i = 0; i < kEncBuckets; i++) cnt[i] = u.pr.bal_cnt[i];
+      uint32_t b = 0, idx = 0;
+      if (enc_bal_item(cnt, tid, b, idx)) {
+        const uint32_t q = u.pr.bal_list[b * kTile + idx], e = u.pr.bal_ver[q];
+        uint8_t* kb = kbytes + q * kFastKeyStride;
+        uint32_t kl = 0;
+        const uint32_t st = deb_fast_key(reinterpret_cast<const uint8_t*>(buf) + (e & 0xFFFFu), e >> 16, kb, u.pr.tab, kl);
+        static_assert(kFastKeyStride == 44 && kFastKeyCap + 5 <= 40, "slot bytes 40..43 are free");
+        reinterpret_cast<uint32_t*>(kb)[10] = st | (kl << 8);
+      }
+      __syncthreads();  // the keys are in their packages' slots
+    }
+    if (packed && listed) {
+      const uint32_t w = reinterpret_cast<const uint32_t*>(kbytes + tid * kFastKeyStride)[10];
+      pre.fast_st = w & 0xFFu;
+      pre.fast_kl = w >> 8;
+      probe_one<GM, uint32_t, 0, 2>(a, p, d.x, nlen, vlen, sb, sb + nlen, w0 + off + nlen, r,
+                                    kbytes + tid * kFastKeyStride, u.pr.tab, &pre);
+    } else if (own && (!packed || pre.found)) {
+      // rare: lane per package, as without the list - a tile with a window that is not staged, or
+      // a platform of another grammar (an absent name of a packed tile: no key, no rows)
+      if (staged) {
+        probe_one<GM, uint32_t, 0>(a, p, d.x, nlen, vlen, sb, sb + nlen, w0 + off + nlen, r,
+                                   kbytes + tid * kFastKeyStride, u.pr.tab);
+      } else {
+        const uint8_t* gb = a.arena + w0 + off;
+        probe_one<GM, uint32_t, 0>(a, p, d.x, nlen, vlen, gb, gb + nlen, w0 + off + nlen, r);
+      }
+    }
+  } else if (p < a.n && d.x < a.db.n_plats) {
     if (staged) {
       const uint8_t* sb = reinterpret_cast<const uint8_t*>(sbuf) + uint32_t(w0 - base16) + off;
-      probe_one<GM, uint32_t, DIAG & 3>(a, p, d.x, nlen, vlen, sb, sb + nlen, w0 + off + nlen, r,
-                                        reinterpret_cast<uint8_t*>(u.pr.kbuf) + tid * kFastKeyStride, u.pr.tab);
+      probe_one<GM, uint32_t, DIAG & 11>(a, p, d.x, nlen, vlen, sb, sb + nlen, w0 + off + nlen, r,
+                                         reinterpret_cast<uint8_t*>(u.pr.kbuf) + tid * kFastKeyStride, u.pr.tab);
     } else {
       const uint8_t* gb = a.arena + w0 + off;
       probe_one<GM, uint32_t, DIAG & 3>(a, p, d.x, nlen, vlen, gb, gb + nlen, w0 + off + nlen, r);
@@ -1230,8 +1340,9 @@ void launch_fused(uint32_t n_tiles, hipStream_t st, const FusedArgs& a) {
 // Table entry of variant (F, K, MB) for grammar set GM / row-filter level FILT
 // (match_variants.h: F = 0 split, 1-3 fused, 4 fused with per-wave sweep segments, 5 also
 // per-wave staging, 6 the same held at 6 waves, 7 per-wave staging + segments over the hot rows
-// (DB::rows16, dpkg-only), 8 the same with rank-indexed windows and the one-compare pair test, 11-15
-// and 25-26 fused measurement builds).
+// (DB::rows16, dpkg-only), 8 the same with rank-indexed windows and the one-compare pair test, 9
+// that kernel with the tile's encoder work list (fused_kernel kBal), 11-15, 25-26 and 28 fused
+// measurement builds).
 template <uint32_t GM, int FILT, int F, int K, int MB>
 constexpr FusedFn fused_entry() {
   if constexpr (F == 0) return nullptr;
@@ -1244,8 +1355,14 @@ constexpr FusedFn fused_entry() {
   } else if constexpr (F == 8) {  // the same with rank-indexed windows and the one-compare pair test (sweep_seg REC)
     if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | 12 | 16>;
     else return nullptr;
+  } else if constexpr (F == 9) {  // F = 8 with the tile's encoder work list (fused_kernel kBal)
+    if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | 12 | 16 | 32>;
+    else return nullptr;
   } else if constexpr (F == 25 || F == 26) {  // TVM_DIAG: 16-byte row loads, dpkg-only
     if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | (F == 25 ? 4 : 8)>;
+    else return nullptr;
+  } else if constexpr (F == 28) {  // TVM_DIAG: F = 8 with the fast encoder cut to 12 bytes, dpkg-only
+    if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 8, 1, 3 | 12 | 16>;
     else return nullptr;
   }
   // the all-grammar K <= 2 kernels are held at 5 waves per SIMD (96 VGPRs): the Maven program

@@ -17,7 +17,8 @@
   X(6, 3, 2400, "fused_k3_m2400_wseg6") \
   X(7, 4, 2400, "fused_k4_m2400_wseg_r16") \
   X(7, 8, 2400, "fused_k8_m2400_wseg_r16") \
-  X(8, 4, 2400, "fused_k4_m2400_wseg_rec_r16")
+  X(8, 4, 2400, "fused_k4_m2400_wseg_rec_lane_r16") \
+  X(9, 4, 2400, "fused_k4_m2400_wseg_rec_r16")
 
 // Measurement-only variants (wrong match lists by construction): built only with
 // `make DIAG=1` (-DTVM_DIAG), never reachable in the product library.
@@ -25,6 +26,10 @@
 // its 32-byte Row - 25 at 16-byte stride (the traffic of a 16-byte row array with the same
 // indices), 26 the first half of the pair's own Row (32-byte stride: the same lines as F = 5,
 // half the bytes into the registers).  The bound on what a 16-byte row layout can gain.
+// F = 28 (dpkg-only): the lane-per-package kernel (F = 8) with every lane's fast encoder given at most the first
+// 12 bytes of its version, so every wave's encoder loops run 3 dword trips.  Against auto it prices
+// an encoder dword trip on hardware: the bound on what balancing the encoder across a tile can gain
+// (tools/encbal_model.py, profiles/encbal/upper_bound.txt).
 #ifdef TVM_DIAG
 #define TVM_MATCH_VARIANTS(X)      \
   TVM_MATCH_VARIANTS_PRODUCT(X)    \
@@ -34,7 +39,8 @@
   X(15, 4, 2048, "diag_stage_only") \
   X(25, 4, 2400, "diag_row16_k4")  \
   X(25, 8, 2400, "diag_row16_k8")  \
-  X(26, 4, 2400, "diag_row16s_k4")
+  X(26, 4, 2400, "diag_row16s_k4") \
+  X(28, 4, 2400, "diag_enc12")
 #else
 #define TVM_MATCH_VARIANTS(X) TVM_MATCH_VARIANTS_PRODUCT(X)
 #endif
@@ -60,7 +66,10 @@ constexpr int kNumTuned = 0 TVM_MATCH_VARIANTS(TVM_VARIANT_COUNT_);
 // Since the rank-indexed package windows and the one-compare pair test (sweep_seg REC; C2 sweep,
 // profiles/instr/sweep_c2.txt: 1.5 % under the parent's sweep, 193 fewer vector instructions per wave):
 // fused_k4_m2400_wseg_rec_r16; fused_k4_m2400_wseg_r16 stays as its A/B partner.
-constexpr int kAutoVariant = 11;         // fused_k4_m2400_wseg_rec_r16
+// Since the tile's encoder work list (fused_kernel kBal, F = 9; C2 sweep, profiles/encbal/sweep_c2.txt):
+// that kernel carries the name fused_k4_m2400_wseg_rec_r16, and the kernel that encodes lane per
+// package (F = 8, auto until then) stays in the list as fused_k4_m2400_wseg_rec_lane_r16, its A/B partner.
+constexpr int kAutoVariant = 12;         // fused_k4_m2400_wseg_rec_r16
 constexpr int kAutoVariantFiltered = 1;  // fused_k2_m2048
 // OS grammar sets with row filters (rpm / apk: no library rows): per-wave staging + segments
 // at 6 waves, K = 2 (round 5 sweep, profiles/r05/sweep_c5.txt: C5 2.317 -> 2.283 ms)

@@ -446,6 +446,34 @@ TVM_HD uint32_t deb_fast_key(const uint8_t* s, uint32_t n, uint8_t* kb, const ui
   return FAST_OK;
 }
 
+// ---- encoder work list of a tile (match_kernel.h fused_kernel, SEG bit 5) ---------------------
+//
+// deb_fast_key's loops run to the longest version of a wave, so the balanced kernel lists the
+// tile's packages that need a key by the dword count of their version (bucket b: b dwords, the
+// last bucket everything longer) and hands them out longest bucket first: work item i of the tile
+// is the (i - items of the longer buckets)-th entry of its bucket's region.
+constexpr uint32_t kEncBuckets = 8;
+TVM_HD uint32_t enc_bal_bucket(uint32_t n) {
+  const uint32_t d = (n + 3) >> 2;
+  return d < kEncBuckets - 1 ? d : kEncBuckets - 1;
+}
+// Work item -> its bucket and its index in the bucket's region, given the buckets' entry counts;
+// false past the end of the list.  Branch-free: one compare per bucket.
+TVM_HD bool enc_bal_item(const uint32_t* cnt, uint32_t item, uint32_t& bucket, uint32_t& idx) {
+  uint32_t end = 0, first = 0, k = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < kEncBuckets; j++) {
+    end += cnt[kEncBuckets - 1 - j];
+    const bool past = item >= end;
+    first = past ? end : first;
+    k += past ? 1u : 0u;
+  }
+  if (k >= kEncBuckets) return false;
+  bucket = kEncBuckets - 1 - k;
+  idx = item - first;
+  return true;
+}
+
 // ------------------------------------------------------------------- signed integers -----
 // Order-preserving variable-length code of a signed 64-bit value: v >= 0 as 0x80+k then
 // k big-endian bytes (k minimal, 0 for v = 0); v < 0 as 0x7F-k then the k bytes of
