@@ -187,6 +187,15 @@ int tvm_engine_verify(tvm_engine* e, char* err, size_t errlen);
  * previous one.  v < 0 only queries.  Names via tvm_variant_name (NULL past the last);
  * variant 0 = "auto" (default): the tuned variant for the batch's grammar set. */
 int tvm_engine_set_variant(tvm_engine* e, int v);
+/* Tuning knob, read at every upload: the tile count from which a batch without library grammars
+ * gets a launch order (heaviest tiles first) and a tile-head record per grid position (default
+ * 1024; batches with library grammars get both from two tiles on).  Returns the previous value;
+ * n = 0 only queries; -1 without an engine. */
+int64_t tvm_engine_set_order_min_tiles(tvm_engine* e, uint32_t n);
+/* Kernel launches of the engine's last device-resident pass (tvm_match_launch) that read tile-head
+ * records: 0 none (no order, or TVM_NO_TILE_HEAD), 1, or 2 for a pass split into a lean and an
+ * all-grammar launch; -1 without an engine. */
+int tvm_engine_last_head_launches(tvm_engine* e);
 const char* tvm_variant_name(int v);
 /* Batches variant v runs: bit 0 dpkg-only, bit 1 OS grammars (dpkg / apk / rpm), bit 2 any
  * grammar; a launch of a variant not built for the batch fails with TVM_EDEVICE. */
@@ -342,6 +351,18 @@ int tvm_deb_fast_key_slot_host(const char* s, size_t n, uint32_t shift, uint8_t*
 int tvm_enc_bal_buckets_host(void);
 int tvm_enc_bal_bucket_host(uint32_t version_len);
 int tvm_enc_bal_item_host(const uint32_t* counts, uint32_t item, uint32_t* bucket, uint32_t* index);
+/* What an upload builds for the ordered launch, host-side for tests: the packages of n_runs runs
+ * (run r: run_n[r] packages of bucket run_bucket[r]; strings as tvm_batch_add_many, indexed over
+ * all runs) as one batch.  toff_out: the batch's group offsets padded to whole tiles plus the
+ * arena end (4 * tiles + 1 words); order_out: grid position -> tile; heads_out: one 32-byte record
+ * per grid position {u64 base, u32 tile, u32 delta[4], u32 pad}, the tile's five offsets being
+ * base, base + delta[0..3].  min_tiles as tvm_engine_set_order_min_tiles (0: the default).
+ * Returns the number of records, 0 when the batch lies below the ordering threshold (only
+ * toff_out is written), -1 on bad arguments or more than cap_tiles tiles. */
+int64_t tvm_tile_heads_host(const tvm_db* db, size_t n_runs, const char* const* run_bucket, const uint64_t* run_n,
+                            const char* arena, const uint64_t* name_off, const uint32_t* name_len,
+                            const uint64_t* ver_off, const uint32_t* ver_len, uint32_t min_tiles, uint32_t* order_out,
+                            uint8_t* heads_out, uint64_t* toff_out, size_t cap_tiles);
 /* Host-side compare.IsVulnerable through the load-time interval compiler (tests): 1/0, -1
  * when the advisory JSON does not decode.  Maven: the rows the product builds - intervals for
  * an advisory whose bounds are all numeric, else the pairwise program - so it mirrors the

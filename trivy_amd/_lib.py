@@ -145,6 +145,8 @@ _SIG = [
     ("tvm_engine_table_bytes", ctypes.c_uint64, [_P]),
     ("tvm_engine_verify", ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_engine_set_variant", ctypes.c_int, [_P, ctypes.c_int]),
+    ("tvm_engine_set_order_min_tiles", ctypes.c_int64, [_P, ctypes.c_uint32]),
+    ("tvm_engine_last_head_launches", ctypes.c_int, [_P]),
     ("tvm_variant_name", ctypes.c_char_p, [ctypes.c_int]),
     ("tvm_variant_grammar_sets", ctypes.c_int, [ctypes.c_int]),
     ("tvm_engine_last_variant", ctypes.c_int, [_P]),
@@ -240,6 +242,10 @@ _SIG = [
     ("tvm_enc_bal_bucket_host", ctypes.c_int, [ctypes.c_uint32]),
     ("tvm_enc_bal_item_host", ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
                                              ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("tvm_tile_heads_host", ctypes.c_int64, [_P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.c_void_p,
+                                             ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_size_t]),
     ("tvm_db_advisory_vuln_id", ctypes.c_char_p, [_P, ctypes.c_uint32]),
     ("tvm_version_class", ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_lib_is_vulnerable_host", ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,

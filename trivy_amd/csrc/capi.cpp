@@ -518,6 +518,12 @@ int tvm_engine_set_variant(tvm_engine* e, int v) {
   return v < 0 ? e->eng->variant() : e->eng->set_variant(v);
 }
 
+int64_t tvm_engine_set_order_min_tiles(tvm_engine* e, uint32_t n) {
+  if (!e) return -1;
+  std::unique_lock<std::shared_mutex> lk(e->mu);
+  return int64_t(e->eng->set_order_min_tiles(n));
+}
+
 const char* tvm_variant_name(int v) { return variant_name(v); }
 int tvm_variant_grammar_sets(int v) { return variant_grammar_sets(v); }
 
@@ -525,6 +531,12 @@ int tvm_engine_last_variant(tvm_engine* e) {
   if (!e) return -1;
   std::shared_lock<std::shared_mutex> lk(e->mu);
   return e->eng->last_launched();
+}
+
+int tvm_engine_last_head_launches(tvm_engine* e) {
+  if (!e) return -1;
+  std::shared_lock<std::shared_mutex> lk(e->mu);
+  return e->eng->last_head_launches();
 }
 
 static int detect_common(tvm_engine* e, bool full, const char* fam, const char* ver, const tvm_repository* repo,
@@ -602,6 +614,7 @@ void tvm_batch_free(tvm_batch* b) {
     for (void* p : {static_cast<void*>(b->dev.pk), static_cast<void*>(b->dev.tile_off), static_cast<void*>(b->dev.arena),
                     static_cast<void*>(b->dev.attr), static_cast<void*>(b->dev.cpe_bits), static_cast<void*>(b->dev.rec),
                     static_cast<void*>(b->dev.tail), static_cast<void*>(b->dev.spill),
+                    static_cast<void*>(b->dev.tile_map), static_cast<void*>(b->dev.tile_head),
                     static_cast<void*>(b->external_out ? nullptr : b->m.pkg),
                     static_cast<void*>(b->external_out ? nullptr : b->m.adv), static_cast<void*>(b->m.dir),
                     static_cast<void*>(b->m.ctl),
@@ -1177,6 +1190,36 @@ int tvm_enc_bal_item_host(const uint32_t* counts, uint32_t item, uint32_t* bucke
   *bucket = b;
   *index = i;
   return 1;
+}
+
+int64_t tvm_tile_heads_host(const tvm_db* db, size_t n_runs, const char* const* run_bucket, const uint64_t* run_n,
+                            const char* arena, const uint64_t* name_off, const uint32_t* name_len,
+                            const uint64_t* ver_off, const uint32_t* ver_len, uint32_t min_tiles, uint32_t* order_out,
+                            uint8_t* heads_out, uint64_t* toff_out, size_t cap_tiles) {
+  if (!db || !db->finalized || (n_runs && (!run_bucket || !run_n))) return -1;
+  HostBatch hb;
+  size_t i = 0;
+  for (size_t r = 0; r < n_runs; r++) {
+    if (!run_bucket[r] || (run_n[r] && (!arena || !name_off || !name_len || !ver_off || !ver_len))) return -1;
+    const int32_t plat = db->db.find_plat(run_bucket[r]);
+    for (uint64_t k = 0; k < run_n[r]; k++, i++)
+      hb.add(plat < 0 ? 0xFFFFFFFFu : uint32_t(plat), std::string_view(arena + name_off[i], name_len[i]),
+             std::string_view(arena + ver_off[i], ver_len[i]));
+  }
+  const uint32_t nt = hb.n_tiles();
+  if (nt > cap_tiles) return -1;
+  std::vector<uint64_t> toff(hb.tile_off.begin(), hb.tile_off.end());  // as Engine::upload pads them
+  toff.resize(size_t(nt) * kGroupsPerTile + 1, hb.arena.size());
+  if (toff_out) std::memcpy(toff_out, toff.data(), toff.size() * 8);
+  std::vector<uint32_t> order;
+  uint32_t n_lean = 0;
+  if (!tile_order(db->db, hb, batch_grammar_set(db->db, hb), min_tiles ? min_tiles : kOrderMinTiles, order, n_lean))
+    return 0;
+  std::vector<TileHead> heads;
+  build_tile_heads(toff, order, heads);
+  if (order_out) std::memcpy(order_out, order.data(), order.size() * 4);
+  if (heads_out) std::memcpy(heads_out, heads.data(), heads.size() * sizeof(TileHead));
+  return int64_t(order.size());
 }
 
 int tvm_lib_is_vulnerable_host(int grammar, const char* ver, size_t ver_len, const char* advisory_json,

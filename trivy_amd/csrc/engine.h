@@ -98,6 +98,28 @@ struct PkgRec {
   uint64_t k0, k1, k2;  // the installed key's first 24 bytes, big-endian (rows compare 24-byte heads)
 };
 
+// What a match workgroup needs to start its tile, one 32-byte record per grid position of an
+// ordered launch (DevBatch::tile_head): the tile it takes and the arena offsets of the tile's
+// four 64-package groups and their end, tile_off[4 * tile + i] = base + (i ? d[i - 1] : 0).
+// A tile's strings span less than 4 GiB (256 packages of two 16-bit lengths).
+struct alignas(32) TileHead {
+  uint64_t base;
+  uint32_t tile;
+  uint32_t d[kGroupsPerTile];
+  uint32_t pad;
+};
+static_assert(sizeof(TileHead) == 32, "one record per 32 bytes");
+
+// The records of `order` (grid position -> tile) over toff, the batch's group offsets padded to
+// whole tiles plus the arena end (Engine::upload).
+void build_tile_heads(const std::vector<uint64_t>& toff, const std::vector<uint32_t>& order, std::vector<TileHead>& out);
+// Grammar bits (1 << Cmp) of the platforms a batch touches, and the launch order Engine::upload
+// gives its tiles (engine.hip; host only, no device needed).
+constexpr uint32_t kOrderMinTiles = 1024;
+uint32_t batch_grammar_set(const DB& db, const HostBatch& hb);
+bool tile_order(const DB& db, const HostBatch& hb, uint32_t gm, uint32_t min_tiles, std::vector<uint32_t>& order,
+                uint32_t& n_lean_tiles);
+
 struct DevBatch {
   uint2* pk = nullptr;
   uint64_t* tile_off = nullptr;
@@ -118,6 +140,9 @@ struct DevBatch {
   // the heaviest tiles first, so the launch does not end on a tail of Maven-program tiles);
   // nullptr = tile order
   uint32_t* tile_map = nullptr;
+  // beside tile_map and in its order: the tile and its group offsets per grid position, so a
+  // workgroup's first trip brings both (nullptr with TVM_NO_TILE_HEAD: offsets from tile_off)
+  TileHead* tile_head = nullptr;
   // batches of the all-grammar set: the first n_lean_tiles entries of tile_map are the tiles
   // without Maven / RubyGems packages, matched by the GM_LEAN kernel in a launch of their own
   // (Engine::launch); the rest take the all-grammar kernel
@@ -398,11 +423,12 @@ class Engine {
   // behind event `ev` (the caller zeroes m.ctl once before the first chunk).
   // co: a previous chunk's result move, run by extra workgroups of this launch (fused
   // variants) or by its own kernel ahead of it (split variants).
-  // tmap / tmap_n / gm: (fused variants, whole batch) the launch's grid is tmap_n workgroups
-  // over the tiles tmap lists, with the kernel of grammar set gm
+  // tmap_off / tmap_n / gm: (fused variants, whole batch, tmap_n > 0) the launch's grid is tmap_n
+  // workgroups over grid positions [tmap_off, tmap_off + tmap_n) of the batch's tile order (and
+  // of its head records), with the kernel of grammar set gm
   bool launch_tiles(const DevBatch& b, const DevMatches& m, uint32_t t_begin, uint32_t t_end, hipStream_t probe_st,
                     hipStream_t sweep_st, hipEvent_t ev, std::string& err, const CopyOutArgs* co = nullptr,
-                    unsigned long long* ctl_zero = nullptr, const uint32_t* tmap = nullptr, uint32_t tmap_n = 0,
+                    unsigned long long* ctl_zero = nullptr, uint32_t tmap_off = 0, uint32_t tmap_n = 0,
                     uint32_t gm = 0);
 
   // After the pass: the match list as {package, advisory} pairs in (package, advisory) order.
@@ -424,14 +450,22 @@ class Engine {
   // Sweep-kernel variant (pairs per lane / LDS buffer); returns the previous one.  Default
   // 0 = "auto", overridable with the TVM_VARIANT environment variable at open().
   int set_variant(int v);
+  // Tiles from which a batch without library grammars gets a launch order and head records at
+  // upload (default kOrderMinTiles; batches with library grammars: always more than one tile);
+  // returns the previous value, n = 0 only queries.  Read at every upload.
+  uint32_t set_order_min_tiles(uint32_t n);
   int last_launched() const { return last_launched_; }
+  // Kernel launches of the last launch() that read tile-head records (0: none; 2: a split pass).
+  int last_head_launches() const { return last_head_launches_; }
   bool verify(std::string& err);
   int variant() const { return variant_; }
 
  private:
   int dev_ = 0;
   int variant_ = 0;
+  uint32_t order_min_tiles_ = kOrderMinTiles;
   std::atomic<int> last_launched_{-1};
+  std::atomic<int> last_head_launches_{0};
   hipStream_t stream_ = nullptr;
   const DB* db_ = nullptr;
   DevDB d_;

@@ -212,9 +212,17 @@ int Engine::set_variant(int v) {
   return old;
 }
 
+uint32_t Engine::set_order_min_tiles(uint32_t n) {
+  const uint32_t old = order_min_tiles_;
+  if (n) order_min_tiles_ = n;
+  return old;
+}
+
 // Grammar bits (1 << Cmp) of the platforms a batch touches.
-uint32_t Engine::grammar_set(const HostBatch& hb) const {
-  const auto& pi = db_->plat_info;
+uint32_t Engine::grammar_set(const HostBatch& hb) const { return batch_grammar_set(*db_, hb); }
+
+uint32_t batch_grammar_set(const DB& db, const HostBatch& hb) {
+  const auto& pi = db.plat_info;
   std::atomic<uint32_t> gm{0};
   range_for(hb.pk.size(), 1 << 18, [&](size_t a, size_t b) {  // host threads: a fresh batch's prepare
     uint32_t g = 0, last = 0xFFFFFFFFu;
@@ -326,34 +334,81 @@ bool Engine::upload(const HostBatch& hb, DevBatch& b, std::string& err) {
   if (!hb.attr.empty() &&
       !hip_ok(hipMemcpy(b.attr, hb.attr.data(), hb.attr.size() * sizeof(uint2), hipMemcpyHostToDevice), "H2D attr", err))
     return false;
+  std::vector<uint32_t> order;
+  if (tile_order(*db_, hb, b.gm, order_min_tiles_, order, b.n_lean_tiles)) {
+    if (!dmalloc(&b.tile_map, order.size(), "hipMalloc(tile order)", err) ||
+        !hip_ok(hipMemcpy(b.tile_map, order.data(), order.size() * 4, hipMemcpyHostToDevice), "H2D tile order", err))
+      return false;
+    // the tile's head record per grid position (TVM_NO_TILE_HEAD, measurement: the order alone,
+    // offsets from tile_off; read at every upload)
+    if (!std::getenv("TVM_NO_TILE_HEAD")) {
+      std::vector<TileHead> heads;
+      build_tile_heads(toff, order, heads);
+      if (!dmalloc(&b.tile_head, heads.size(), "hipMalloc(tile heads)", err) ||
+          !hip_ok(hipMemcpy(b.tile_head, heads.data(), heads.size() * sizeof(TileHead), hipMemcpyHostToDevice),
+                  "H2D tile heads", err))
+        return false;
+    }
+  }
+  if (!hb.cpe_bits.empty() && hb.cpe_words) {
+    if (!dmalloc(&b.cpe_bits, hb.cpe_bits.size(), "hipMalloc(cpe sets)", err) ||
+        !hip_ok(hipMemcpy(b.cpe_bits, hb.cpe_bits.data(), hb.cpe_bits.size() * 4, hipMemcpyHostToDevice), "H2D cpe", err))
+      return false;
+    b.cpe_words = hb.cpe_words;
+    b.n_cpe_sets = uint32_t(hb.cpe_bits.size() / hb.cpe_words);
+  }
+  return true;
+}
+
+void build_tile_heads(const std::vector<uint64_t>& toff, const std::vector<uint32_t>& order, std::vector<TileHead>& out) {
+  out.resize(order.size());
+  for (size_t i = 0; i < order.size(); i++) {
+    const uint64_t* o = toff.data() + size_t(order[i]) * kGroupsPerTile;
+    TileHead& h = out[i];
+    h.base = o[0];
+    h.tile = order[i];
+    for (int k = 0; k < kGroupsPerTile; k++) h.d[k] = uint32_t(o[k + 1] - o[0]);
+    h.pad = 0;
+  }
+}
+
+// The launch order of a batch's tiles (grid position -> tile) and the count of lean tiles at
+// its head; false (nothing built) for a batch below the ordering threshold: more than one tile
+// with a library grammar, min_tiles (Engine::set_order_min_tiles) without.  Host only.
+bool tile_order(const DB& db, const HostBatch& hb, uint32_t gm, uint32_t min_tiles, std::vector<uint32_t>& order,
+                uint32_t& n_lean_tiles) {
+  const uint32_t n_tiles = hb.n_tiles();
+  order.clear();
+  n_lean_tiles = 0;
   static const bool no_order = std::getenv("TVM_NO_TILE_ORDER") != nullptr;  // measurement: tile order
-  if (((b.gm & ~GM_OS) != 0 ? b.n_tiles > 1 : b.n_tiles >= 1024) && !no_order) {
+  if (no_order || !((gm & ~GM_OS) != 0 ? n_tiles > 1 : n_tiles >= std::max(min_tiles, 1u))) return false;
+  {
     // the device-resident launch takes the tiles heaviest first (predicted rows from the host
     // index, Maven rows weighted 8x: a program row costs many interval rows), so the grid does
     // not end on a tail of heavy tiles - C2's row counts per tile are heavy-tailed (median
     // 2.1k pairs, p99 5.5k, max 11.9k): 0.425 -> 0.416 ms; C3 0.216 -> 0.211 ms
-    const auto& pi = db_->plat_info;
+    const auto& pi = db.plat_info;
     std::vector<uint64_t> off;
     hb.name_offsets(off);
-    std::vector<uint64_t> w(b.n_tiles, 0);
-    range_for(b.n_tiles, 64, [&](size_t t0, size_t t1) {
+    std::vector<uint64_t> w(n_tiles, 0);
+    range_for(n_tiles, 64, [&](size_t t0, size_t t1) {
       for (size_t t = t0; t < t1; t++) {
         uint64_t s = 0;
         for (size_t p = t * kTile; p < std::min(hb.pk.size(), (t + 1) * kTile); p++) {
           const uint32_t plat = hb.pk[p].x;
           if (plat >= pi.size()) continue;
           const std::string_view name(reinterpret_cast<const char*>(hb.arena.data()) + off[p], hb.pk[p].y & 0xFFFFu);
-          s += 1 + uint64_t(db_->key_rows(plat, name)) * (pi[plat].cmp == CMP_MAVEN ? 8 : 1);
+          s += 1 + uint64_t(db.key_rows(plat, name)) * (pi[plat].cmp == CMP_MAVEN ? 8 : 1);
         }
         w[t] = s;
       }
     });
     // all-grammar batches: the tiles without Maven / RubyGems packages first (their own launch
     // on the GM_LEAN kernel, Engine::launch), each part heaviest first
-    std::vector<uint8_t> full(b.n_tiles, 1);
+    std::vector<uint8_t> full(n_tiles, 1);
     static const bool no_lean = std::getenv("TVM_NO_LEAN") != nullptr;
-    if (grammar_index(b.gm) == 2 && !no_lean)
-      range_for(b.n_tiles, 64, [&](size_t t0, size_t t1) {
+    if (grammar_index(gm) == 2 && !no_lean)
+      range_for(n_tiles, 64, [&](size_t t0, size_t t1) {
         for (size_t t = t0; t < t1; t++) {
           bool f = false;
           for (size_t p = t * kTile; p < std::min(hb.pk.size(), (t + 1) * kTile) && !f; p++) {
@@ -363,16 +418,15 @@ bool Engine::upload(const HostBatch& hb, DevBatch& b, std::string& err) {
           full[t] = f;
         }
       });
-    std::vector<uint32_t> order(b.n_tiles);
-    for (uint32_t t = 0; t < b.n_tiles; t++) order[t] = t;
-    b.n_lean_tiles = 0;
-    for (uint32_t t = 0; t < b.n_tiles; t++) b.n_lean_tiles += full[t] ? 0 : 1;
+    order.resize(n_tiles);
+    for (uint32_t t = 0; t < n_tiles; t++) order[t] = t;
+    for (uint32_t t = 0; t < n_tiles; t++) n_lean_tiles += full[t] ? 0 : 1;
     // a batch Engine::launch splits keeps its parts apart (lean tiles first); one launch over
     // every tile takes them heaviest first whatever their kernel part (TVM_TILE_ORDER=lean:
     // the parts apart anyway, =full: the all-grammar tiles first - measurement only)
     static const char* ord = std::getenv("TVM_TILE_ORDER");
-    const uint32_t n_full = b.n_tiles - b.n_lean_tiles;
-    const bool split = n_full && n_full < b.n_tiles && n_full * kSplitFull <= b.n_tiles;
+    const uint32_t n_full = n_tiles - n_lean_tiles;
+    const bool split = n_full && n_full < n_tiles && n_full * kSplitFull <= n_tiles;
     const int mode = split || (ord && std::strcmp(ord, "lean") == 0) ? 0 : (ord && std::strcmp(ord, "full") == 0) ? 1 : 2;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
       if (mode == 0 && full[x] != full[y]) return full[x] < full[y];
@@ -383,18 +437,8 @@ bool Engine::upload(const HostBatch& hb, DevBatch& b, std::string& err) {
     // two grammars' code and rows per XCD); the dpkg and rpm / apk kernels keep the global
     // heaviest-first order (C2 0.383 -> 0.393, C5 1.81 -> 2.40 ms with the runs: per-platform
     // runs of equal predicted rows are not equal work there; profiles/r06/xcd/)
-    if (mode == 2 && grammar_index(b.gm) == 2 && !(ord && std::strcmp(ord, "w") == 0) && b.n_tiles >= 8 * kXcds)
+    if (mode == 2 && grammar_index(gm) == 2 && !(ord && std::strcmp(ord, "w") == 0) && n_tiles >= 8 * kXcds)
       xcd_order(hb, w, order);
-    if (!dmalloc(&b.tile_map, order.size(), "hipMalloc(tile order)", err) ||
-        !hip_ok(hipMemcpy(b.tile_map, order.data(), order.size() * 4, hipMemcpyHostToDevice), "H2D tile order", err))
-      return false;
-  }
-  if (!hb.cpe_bits.empty() && hb.cpe_words) {
-    if (!dmalloc(&b.cpe_bits, hb.cpe_bits.size(), "hipMalloc(cpe sets)", err) ||
-        !hip_ok(hipMemcpy(b.cpe_bits, hb.cpe_bits.data(), hb.cpe_bits.size() * 4, hipMemcpyHostToDevice), "H2D cpe", err))
-      return false;
-    b.cpe_words = hb.cpe_words;
-    b.n_cpe_sets = uint32_t(hb.cpe_bits.size() / hb.cpe_words);
   }
   return true;
 }
@@ -407,6 +451,7 @@ void Engine::free_batch(int device, DevBatch& b, bool pooled) {
     dfree(p, pooled, device);
   dfree(b.cpe_bits, false, device);  // never pooled (copied by the caller)
   dfree(b.tile_map, false, device);
+  dfree(b.tile_head, false, device);
   b = DevBatch{};
 }
 
@@ -457,7 +502,7 @@ bool Engine::fetch_ordered(const DevMatches& m, uint32_t n_pkgs, uint64_t total,
 
 bool Engine::launch_tiles(const DevBatch& b, const DevMatches& m, uint32_t t_begin, uint32_t t_end, hipStream_t pst,
                           hipStream_t sst, hipEvent_t ev, std::string& err, const CopyOutArgs* co,
-                          unsigned long long* ctl_zero, const uint32_t* tmap, uint32_t tmap_n, uint32_t gm) {
+                          unsigned long long* ctl_zero, uint32_t tmap_off, uint32_t tmap_n, uint32_t gm) {
   (void)hipSetDevice(dev_);
   if (t_end > b.n_tiles) t_end = b.n_tiles;
   if (t_begin >= t_end) return true;
@@ -467,8 +512,10 @@ bool Engine::launch_tiles(const DevBatch& b, const DevMatches& m, uint32_t t_beg
   }
   if (!gm) gm = b.gm;
   const int vi = resolve_variant(variant_, gm);
-  if (tmap && (co || t_begin != 0 || t_end != b.n_tiles || !kFusedVariant[vi - 1] || tmap_n == 0)) {
-    err = "a tile-list launch is a fused pass over the whole batch";
+  const bool part = tmap_n != 0;  // grid positions [tmap_off, tmap_off + tmap_n) of the batch's tile order
+  if (part && (co || t_begin != 0 || t_end != b.n_tiles || !kFusedVariant[vi - 1] || !b.tile_map ||
+               uint64_t(tmap_off) + tmap_n > b.n_tiles)) {
+    err = "a tile-list launch is a fused pass over the whole batch, on a part of its tile order";
     return false;
   }
   last_launched_ = vi;
@@ -540,14 +587,20 @@ bool Engine::launch_tiles(const DevBatch& b, const DevMatches& m, uint32_t t_beg
       }();
       fa.n_copy = n_copy;
     }
-    if (!co && t_begin == 0 && t_end == b.n_tiles) fa.tile_map = tmap ? tmap : b.tile_map;
+    if (!co && t_begin == 0 && t_end == b.n_tiles) {
+      // the head records lie in tile_map's order: a launch over a part of it takes the same part
+      const uint32_t off = part ? tmap_off : 0u;
+      if (b.tile_map) fa.tile_map = b.tile_map + off;
+      if (b.tile_map && b.tile_head) fa.tile_head = b.tile_head + off;
+    }
+    if (fa.tile_head) last_head_launches_++;
     fa.ctl_zero = co ? nullptr : ctl_zero;
     const FusedFn fn = fused_fn(gm, vi);
     if (!fn) {
       err = std::string("match-path variant ") + kVariantNames[vi - 1] + " is not built for this batch's grammar set";
       return false;
     }
-    fn(tmap ? tmap_n : nt, pst, fa);
+    fn(part ? tmap_n : nt, pst, fa);
     return hip_ok(hipGetLastError(), "match kernel launch", err);
   }
   const bool filt = (b.gm & ~GM_DEB) != 0;
@@ -557,6 +610,7 @@ bool Engine::launch_tiles(const DevBatch& b, const DevMatches& m, uint32_t t_beg
 
 bool Engine::launch(const DevBatch& b, DevMatches& m, hipStream_t st, std::string& err) {
   (void)hipSetDevice(dev_);
+  last_head_launches_ = 0;
   unsigned long long* zero = nullptr;  // the control block this pass leaves behind
   if (m.ctl_next) {
     std::swap(m.ctl, m.ctl_next);  // count into the block the last pass zeroed
@@ -578,8 +632,8 @@ bool Engine::launch(const DevBatch& b, DevMatches& m, hipStream_t st, std::strin
   const uint32_t nl = b.n_lean_tiles;
   if (nl && nl < b.n_tiles && (b.n_tiles - nl) * kSplitFull <= b.n_tiles && b.tile_map && grammar_index(b.gm) == 2 &&
       kFusedVariant[resolve_variant(variant_, b.gm) - 1] && kFusedVariant[resolve_variant(variant_, GM_LEAN) - 1]) {
-    return launch_tiles(b, m, 0, b.n_tiles, st, st, nullptr, err, nullptr, zero, b.tile_map, nl, GM_LEAN) &&
-           launch_tiles(b, m, 0, b.n_tiles, st, st, nullptr, err, nullptr, nullptr, b.tile_map + nl, b.n_tiles - nl,
+    return launch_tiles(b, m, 0, b.n_tiles, st, st, nullptr, err, nullptr, zero, 0, nl, GM_LEAN) &&
+           launch_tiles(b, m, 0, b.n_tiles, st, st, nullptr, err, nullptr, nullptr, nl, b.n_tiles - nl,
                         b.gm);
   }
   return launch_tiles(b, m, 0, b.n_tiles, st, st, nullptr, err, nullptr, zero);

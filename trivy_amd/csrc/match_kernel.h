@@ -90,6 +90,7 @@ struct FusedArgs {
   CopyOutArgs co;       // end-to-end pipeline: the previous chunk's result move ...
   uint32_t n_copy = 0;  // ... by workgroups [0, n_copy) of this launch (0: none)
   const uint32_t* tile_map = nullptr;  // workgroup -> tile (DevBatch::tile_map; no result move)
+  const TileHead* tile_head = nullptr;  // workgroup -> tile and its group offsets (DevBatch::tile_head), with tile_map
   unsigned long long* ctl_zero = nullptr;  // device-resident pass: the control block to zero for the next
 };
 
@@ -439,26 +440,61 @@ __device__ __forceinline__ void probe_lookup(const ProbeArgs& a, uint32_t p, uin
   }
 }
 
-// A tile's string window (nv 16-byte words, nv <= kStage / 16) into LDS, plus two zero
-// words: every lane issues its (at most kStage / 16 / kTile) loads before storing any.
-template <uint32_t STG = kStage>
-__device__ __forceinline__ void stage_window(uint4* buf, const uint8_t* src8, uint32_t nv, uint32_t tid) {
-  constexpr uint32_t SV = (STG / 16 + kTile - 1) / kTile;
+// A string window (nv 16-byte words) into LDS, plus two zero words, in two steps so that the
+// loads are in flight while the caller does other work (the length scan, which waits for the
+// package words issued just before): window_issue has lane i of W load its SV words into
+// registers, window_store writes them.  Loads and stores are unconditional - a lane past the
+// window re-reads its last word (word 0 of an empty or unstaged window, nv = 0: inside the
+// arena's padding) - because a store under `i + k * W < nv` had its load sunk into the branch
+// by the compiler, one waited trip per k.  The stores stay inside the window's own SV * W words.
+// ZERO: a lane past the window stores zeros (a tile-wide window: its waves are not ordered
+// against the two zero words); a wave's own LDS writes keep their order, so it stores what it
+// loaded and the zero words land behind.
+template <uint32_t SV, uint32_t W>
+__device__ __forceinline__ void window_issue(uint4 (&v)[SV], const uint8_t* src8, uint32_t nv, uint32_t i) {
   const uint4* src = reinterpret_cast<const uint4*>(src8);
-  if (nv) {
-    uint4 v[SV];
+  const uint32_t last = max(nv, 1u) - 1;
 #pragma unroll
-    for (uint32_t k = 0; k < SV; k++) v[k] = src[min(tid + k * kTile, nv - 1)];
-#pragma unroll
-    for (uint32_t k = 0; k < SV; k++)
-      if (tid + k * kTile < nv) buf[tid + k * kTile] = v[k];
-  }
-  if (tid < 2) buf[nv + tid] = make_uint4(0, 0, 0, 0);
+  for (uint32_t k = 0; k < SV; k++) v[k] = src[min(i + k * W, last)];
 }
 
-// Per-wave staging (fused_kernel SEG bit 1): wave w stages its own 64-package group's window
-// (tile_off[g] .. tile_off[g + 1], at most kStage / 4 bytes) into its quarter of the buffer,
-// with a wave scan of the lengths - no workgroup barrier before the probe.
+template <uint32_t SV, uint32_t W, bool ZERO>
+__device__ __forceinline__ void window_store(uint4* buf, const uint4 (&v)[SV], uint32_t nv, uint32_t i) {
+#pragma unroll
+  for (uint32_t k = 0; k < SV; k++) buf[i + k * W] = (!ZERO || i + k * W < nv) ? v[k] : make_uint4(0, 0, 0, 0);
+  if (i < 2) buf[nv + i] = make_uint4(0, 0, 0, 0);
+}
+
+// A tile's window (nv <= STG / 16 words, by all kTile lanes) and a wave's (fused_kernel SEG bit 1:
+// wave w stages its own 64-package group's window, tile_off[g] .. tile_off[g + 1], at most
+// STG / 4 bytes, into its quarter of the buffer, with a wave scan of the lengths - no workgroup
+// barrier before the probe): the words per lane, which fit the window's buffer.
+template <uint32_t STG>
+struct StageGeom {
+  static constexpr uint32_t kTileSV = (STG / 16 + kTile - 1) / kTile;
+  static constexpr uint32_t kWaveSV = (STG / 4 / 16 + 63) / 64;
+  static_assert(kTileSV * kTile <= STG / 16 + 2, "an unconditional store stays inside the tile's window");
+  static_assert(kWaveSV * 64 <= STG / 4 / 16 + 2, "an unconditional store stays inside the wave's window");
+};
+
+// A tile's window in one step, for the kernels that stage behind their length scan.
+template <uint32_t STG = kStage>
+__device__ __forceinline__ void stage_window(uint4* buf, const uint8_t* src8, uint32_t nv, uint32_t tid) {
+  if (nv) {
+    uint4 v[StageGeom<STG>::kTileSV];
+    window_issue<StageGeom<STG>::kTileSV, kTile>(v, src8, nv, tid);
+    window_store<StageGeom<STG>::kTileSV, kTile, true>(buf, v, nv, tid);
+  } else if (tid < 2) {
+    buf[tid] = make_uint4(0, 0, 0, 0);
+  }
+}
+
+// A 64-bit value that every lane of the wave holds alike, as a scalar.
+__device__ __forceinline__ uint64_t wave_uniform(uint64_t v) {
+  return uint64_t(__builtin_amdgcn_readfirstlane(uint32_t(v))) |
+         (uint64_t(__builtin_amdgcn_readfirstlane(uint32_t(v >> 32))) << 32);
+}
+
 __device__ __forceinline__ uint32_t wave_exscan(uint32_t v, uint32_t lane) {
   uint32_t x = v;
 #pragma unroll
@@ -467,21 +503,6 @@ __device__ __forceinline__ uint32_t wave_exscan(uint32_t v, uint32_t lane) {
     if (lane >= uint32_t(d)) x += y;
   }
   return x - v;
-}
-
-template <uint32_t STG = kStage>
-__device__ __forceinline__ void stage_window_wave(uint4* buf, const uint8_t* src8, uint32_t nv, uint32_t lane) {
-  constexpr uint32_t SV = (STG / 4 / 16 + 63) / 64;
-  const uint4* src = reinterpret_cast<const uint4*>(src8);
-  if (nv) {
-    uint4 v[SV];
-#pragma unroll
-    for (uint32_t k = 0; k < SV; k++) v[k] = src[min(lane + k * 64, nv - 1)];
-#pragma unroll
-    for (uint32_t k = 0; k < SV; k++)
-      if (lane + k * 64 < nv) buf[lane + k * 64] = v[k];
-  }
-  if (lane < 2) buf[nv + lane] = make_uint4(0, 0, 0, 0);
 }
 
 template <uint32_t GM, int DIAG = 0>
@@ -493,14 +514,16 @@ __global__ __launch_bounds__(kTile) void probe_kernel(ProbeArgs a) {
   const uint32_t tid = threadIdx.x, t = blockIdx.x;
   if (tid < 128) tab[tid] = deb_fast_code(tid);
   const uint32_t p = t * kTile + tid;
-  uint2 d = make_uint2(0xFFFFFFFFu, 0);
-  if (p < a.n) d = a.pk[p];
+  // through a clamped index (a launch has at least one package), so the load issues beside
+  // the offsets' instead of being waited for inside a branch
+  uint2 d = a.pk[min(p, a.n - 1)];
+  if (p >= a.n) d = make_uint2(0xFFFFFFFFu, 0);
   const uint64_t w0 = a.tile_off[t * kGroupsPerTile], w1 = a.tile_off[(t + 1) * kGroupsPerTile];
   const uint32_t nlen = d.y & 0xFFFFu, vlen = d.y >> 16;
-  uint32_t off = 0;
-  block_exscan<kTile>(wsum, nlen + vlen, tid, off);
   const uint64_t base16 = w0 & ~uint64_t(15);
   const bool staged = w1 - base16 <= kStage;
+  uint32_t off = 0;
+  block_exscan<kTile>(wsum, nlen + vlen, tid, off);
   if (staged) stage_window(stage, a.arena + base16, uint32_t((w1 - base16 + 15) / 16), tid);
   __syncthreads();
   PkgRec r;
@@ -1196,14 +1219,57 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
     }
   }
   const uint32_t tid = threadIdx.x;
-  if (!MOVE && fa.ctl_zero && blockIdx.x == 0 && tid < 8) fa.ctl_zero[tid] = 0ull;  // the next pass's counters
-  const uint32_t t = MOVE ? blockIdx.x - fa.n_copy : (fa.tile_map ? fa.tile_map[blockIdx.x] : blockIdx.x);
-  const uint32_t p = t * kTile + tid;
-  uint2 d = make_uint2(0xFFFFFFFFu, 0);
-  if (p < a.n) d = a.pk[p];
+  // The tile's head: two dependent trips, the grid position's record (tile + group offsets,
+  // DevBatch::tile_head: wave-uniform, scalar loads), then the package words and the string
+  // window together.  Launches without a record (no tile order, the pipelined pass) take
+  // three: tile order, package words beside the group offsets, window.
   constexpr bool kWaveStage = (SEG & 2) != 0;
-  const uint32_t g = t * kGroupsPerTile + (kWaveStage ? (tid >> 6) : 0u);  // the window's first group
-  const uint64_t w0 = a.tile_off[g], w1 = a.tile_off[kWaveStage ? g + 1 : (t + 1) * kGroupsPerTile];  // before the scan's barriers
+  const bool has_head = !MOVE && fa.tile_head != nullptr;
+  uint32_t t;
+  uint64_t w0 = 0, w1 = 0;
+  if (has_head) {
+    const TileHead h = fa.tile_head[blockIdx.x];
+    t = h.tile;
+    if constexpr (kWaveStage) {  // the wave's two offsets, picked with scalar selects
+      const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
+      const uint32_t lo = w == 0 ? 0u : w == 1 ? h.d[0] : w == 2 ? h.d[1] : h.d[2];
+      const uint32_t hi = w == 0 ? h.d[0] : w == 1 ? h.d[1] : w == 2 ? h.d[2] : h.d[3];
+      w0 = h.base + lo;
+      w1 = h.base + hi;
+    } else {
+      w0 = h.base;
+      w1 = h.base + h.d[kGroupsPerTile - 1];
+    }
+  } else {
+    t = MOVE ? blockIdx.x - fa.n_copy : (fa.tile_map ? fa.tile_map[blockIdx.x] : blockIdx.x);
+  }
+  if (!MOVE && fa.ctl_zero && blockIdx.x == 0 && tid < 8) fa.ctl_zero[tid] = 0ull;  // the next pass's counters
+  const uint32_t p = t * kTile + tid;
+  // the package words through a clamped index (a launch has at least one package), selected
+  // afterwards: a load under `p < a.n` was waited for inside its branch, ahead of the offsets
+  uint2 d = a.pk[min(p, a.n - 1)];
+  if (p >= a.n) d = make_uint2(0xFFFFFFFFu, 0);
+  if (!has_head) {
+    // Per-wave staging: a wave's lanes load the same two offsets, so they are read back as
+    // scalars here, which keeps their wait inside this branch.  Left in vector registers they
+    // were merged with the record's offsets at the join, and the join then waited for every
+    // load in flight - the package words of the record's path among them.  Shared staging
+    // keeps them in vector registers: its window loads follow the scan, which waits anyway.
+    const uint32_t g = t * kGroupsPerTile + (kWaveStage ? (tid >> 6) : 0u);  // the window's first group
+    const uint64_t x0 = a.tile_off[g], x1 = a.tile_off[kWaveStage ? g + 1 : (t + 1) * kGroupsPerTile];
+    w0 = kWaveStage ? wave_uniform(x0) : x0;
+    w1 = kWaveStage ? wave_uniform(x1) : x1;
+  }
+  // the window's loads go out here, behind the package words and ahead of the length scan that
+  // waits for those: one wait covers both (an unstaged window: nv = 0, one word that is dropped)
+  constexpr uint32_t kSV = kWaveStage ? StageGeom<STG>::kWaveSV : 1u, kSW = 64;
+  const uint64_t base16 = w0 & ~uint64_t(15);
+  const bool staged = w1 - base16 <= (kWaveStage ? STG / 4 : STG);
+  const uint32_t nv = staged ? uint32_t((w1 - base16 + 15) / 16) : 0u;
+  // (shared staging issues them behind the scan: held across its barriers, the window's words
+  // took those kernels past 96 registers and a wave)
+  uint4 wv[kSV];
+  if constexpr (kWaveStage) window_issue<kSV, kSW>(wv, a.arena + base16, nv, tid & 63);
   if constexpr (kBal) {  // the list's counters, zero before any wave enters a package: under the loads above
     if (tid < kEncBuckets) u.pr.bal_cnt[tid] = 0;
     if (tid == kEncBuckets) u.pr.bal_mixed = 0;
@@ -1212,8 +1278,6 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
   const uint32_t nlen = d.y & 0xFFFFu, vlen = d.y >> 16;
   uint32_t off = 0;
   uint4* sbuf = buf;  // this lane's staging window
-  const uint64_t base16 = w0 & ~uint64_t(15);
-  bool staged;
   const bool own = p < a.n && d.x < a.db.n_plats;
   ProbePre pre;  // kBal
   pre.h = pre.start = 0;
@@ -1224,8 +1288,7 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
   if constexpr (kWaveStage) {
     off = wave_exscan(nlen + vlen, tid & 63);
     sbuf = buf + (tid >> 6) * (STG / 4 / 16 + 2);
-    staged = w1 - base16 <= STG / 4;
-    if (staged) stage_window_wave<STG>(sbuf, a.arena + base16, uint32_t((w1 - base16 + 15) / 16), tid & 63);
+    window_store<kSV, kSW, false>(sbuf, wv, nv, tid & 63);
     if (tid < 128) u.pr.tab[tid] = deb_fast_code(tid);
     if constexpr (kBal) {
       if (!staged) {
@@ -1252,8 +1315,7 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
     __syncthreads();  // the code table (one wave's LDS traffic alone is ordered) and the work list
   } else {
     block_exscan<kTile>(s.wsum[0], nlen + vlen, tid, off);
-    staged = w1 - base16 <= STG;
-    if (staged) stage_window<STG>(buf, a.arena + base16, uint32_t((w1 - base16 + 15) / 16), tid);
+    if (staged) stage_window<STG>(buf, a.arena + base16, nv, tid);
     if (tid < 128) u.pr.tab[tid] = deb_fast_code(tid);
     __syncthreads();
   }
