@@ -734,6 +734,129 @@ int tvm_pipeline_set_filter(tvm_engine* e, tvm_batch* b, const tvm_filter_opts* 
  * without TVM_PIPE_RH_MERGE). */
 int tvm_pipeline_filter_stats(tvm_batch* b, uint64_t out[2]);
 
+/* ---- in-process multi-device: engine groups ---------------------------------------------
+ * One process, several GPUs: the reference serves all concurrent scans from one process
+ * (pkg/rpc/server/server.go:45-56, pkg/k8s/scanner/scanner.go:141); a group lets that process
+ * cut one batch of targets over the GPUs of a node, with no second process and no collective
+ * library.  A group is n engines (the tables replicated per member, as tvm_engine_open
+ * uploads them), a group batch is n member batches - contiguous package ranges cut on target
+ * boundaries, so a Result is never split and per-result dedup / order stay valid on a member -
+ * each with its package base set, so every package index a member reports is global.  A member
+ * is a plain tvm_engine / tvm_batch: every single-engine call works on it and behaves as it
+ * does stand-alone.
+ *
+ * devices[] may name a device more than once (several members on one GPU): that is a test and
+ * fallback shape - the members share one GPU and one link - not a speed-up.
+ * Threads: a group keeps one parked host thread per member beyond the first; none is detached.
+ * tvm_group_close joins them, and so does tvm_shutdown (after which group calls run their
+ * members one after the other on the caller).  Shutdown order for a server: stop issuing calls,
+ * free the group batches, tvm_group_close, tvm_db_free, tvm_shutdown.
+ * Concurrency: one caller uses a given group batch at a time; different group batches on one
+ * group may run concurrently (members take their engines' shared locks, as single batches do);
+ * tvm_group_swap waits for the calls in flight member by member (every group call that reads
+ * the tables, the row pre-probe of tvm_group_batch_add_targets included, holds a member's shared
+ * lock while it does), so the old DB may be freed once it has returned. */
+typedef struct tvm_group tvm_group;
+typedef struct tvm_group_batch tvm_group_batch;
+/* n = 1..8 members on devices[0..n).  On any failure nothing stays open; without a HIP device
+ * it fails with tvm_engine_open's message.  `db` must outlive the group. */
+tvm_group* tvm_group_open(tvm_db* db, const int* devices, int n, char* err, size_t errlen);
+void tvm_group_close(tvm_group* g);
+int tvm_group_size(const tvm_group* g);
+/* Member k, borrowed until tvm_group_close: for drop-in calls (tvm_ospkg_detect, ...) and the
+ * per-member accessors below.  NULL for k out of range.  Never tvm_engine_swap or
+ * tvm_engine_close a member: the members of a group serve one DB and are swapped together
+ * (tvm_group_swap); a member swapped alone leaves group batches with shards on different tables. */
+tvm_engine* tvm_group_engine(tvm_group* g, int k);
+/* tvm_engine_swap for the whole group: every member's new tables are built first (a failure
+ * swaps no member), then each member is swapped under its exclusive lock.  Group batches built
+ * before the swap are refused afterwards with the stale-batch message. */
+int tvm_group_swap(tvm_group* g, tvm_db* db, char* err, size_t errlen);
+/* The shard plan, on the host alone (test hook; trivy_amd/dist.py target_shards in C++):
+ * n_shards + 1 package boundaries over targets given as tvm_batch_add_targets gives them, each
+ * on a target boundary, with near-equal sums of pkg_weight per shard (NULL: 1 per package).
+ * Shards may be empty (more shards than targets). */
+int tvm_group_plan_host(size_t n_targets, const uint64_t* target_end, const uint32_t* pkg_weight, int n_shards,
+                        uint64_t* bounds_out);
+/* Plan modes of tvm_group_batch_add_targets.  PACKAGES (default): a target weighs its package
+ * count - free, and a fleet of thousands of similar targets averages out.  ROWS: a package
+ * weighs its predicted advisory rows + 1, from the host index (the lookup of tvm_db_rows_many,
+ * per run of equal-bucket targets on the host threads) - for few, uneven targets (one image
+ * full of "linux"-like heavy keys) and for batches matched many times.  The pre-probe is one
+ * host index lookup per package.  Measured on the C2 batch (4M packages in 10,000 targets, 16
+ * host threads, tools/group_bench.py): the plan by packages takes 0.011 ms; planning
+ * by rows adds 14-17 ms to the add (the 4M lookups, the sum of the 4M weights and the plan
+ * together: the difference between a group add by rows and one by packages) - against 22-30 ms
+ * for the group add by packages and 2.7 ms for one pipelined pass of that batch. */
+enum { TVM_GROUP_PLAN_PACKAGES = 0, TVM_GROUP_PLAN_ROWS = 1 };
+
+tvm_group_batch* tvm_group_batch_new(tvm_group* g);
+void tvm_group_batch_free(tvm_group_batch* gb);
+/* tvm_batch_cpe_set on every member batch, in the same order on each: the one id they all
+ * gave it, -1 on failure (or after tvm_group_batch_add_targets). */
+int64_t tvm_group_batch_cpe_set(tvm_group_batch* gb, const tvm_str* content_sets, size_t n, tvm_str nvr);
+/* The columns of tvm_batch_add_targets_attrs, once per group batch (a second call is refused):
+ * plans the shards, then builds the member batches, each straight from its slice of the
+ * caller's columns (no intermediate whole batch).  Each member's add is issued from its own host
+ * thread, but every add cuts its work into pieces for the one process-wide pool of host threads,
+ * whose jobs run one at a time: the adds queue behind each other, each on all host threads.  That
+ * is no concurrency win, and none is needed - a group add costs what one add of the whole batch
+ * costs plus the plan (measured: 22-30 ms against 19-25 ms on C2).  Bad arguments and attributes are
+ * refused as the single-batch call refuses them (TVM_EINVAL), before any member is touched. */
+int tvm_group_batch_add_targets(tvm_group_batch* gb, uint32_t plan_mode, size_t n_targets, const tvm_str* buckets,
+                                const uint32_t* target_flags, const uint64_t* target_end, const char* arena,
+                                const uint64_t* name_off, const uint32_t* name_len, const uint64_t* ver_off,
+                                const uint32_t* ver_len, const tvm_attr_cols* attrs);
+int64_t tvm_group_batch_size(const tvm_group_batch* gb);
+/* bounds[0 .. size]: member k holds packages [bounds[k], bounds[k + 1]). */
+int tvm_group_batch_shards(const tvm_group_batch* gb, uint64_t* bounds);
+/* Member k's batch, borrowed until tvm_group_batch_free; NULL for an empty shard.  For
+ * tvm_batch_set_report (first = an index inside the member), the result accessors,
+ * tvm_pipeline_vulns / tvm_match_vulns - with tvm_group_engine(g, k) as the engine. */
+tvm_batch* tvm_group_batch_member(tvm_group_batch* gb, int k);
+
+/* The pipelined pass over a group (the product path).  Prepare: tvm_pipeline_prepare on every
+ * non-empty member with member_caps[k], or with match_cap when member_caps is NULL - always
+ * sufficient, at the price of n match buffers of the whole batch's size (8 bytes of HBM per
+ * entry and member, plus the pinned result of width * match_cap bytes per member); a first
+ * pass's member_matches gives exact caps.  flags pass through (TVM_PIPE_*).  If a member
+ * fails, no member is left prepared.
+ * Set filter: applied to every member; if one refuses, the filter is cleared on all and its
+ * message returned.
+ * Run: the members' tvm_pipeline_run concurrently, one host thread per member (the caller's
+ * serves the first).  ms = wall time of the call; *n_matches = the sum of the raw counts;
+ * member_matches[k] (NULL, or size entries) = member k's raw count, also written on overflow;
+ * TVM_EINVAL on overflow with the sum in *n_matches, as the single call; *err_pkg = the
+ * smallest poisoned global package index, or -1.  After a device error on one member the
+ * others finish, the first error is returned and nothing is retried.
+ * Results: no union copy.  Member k's lists are read with tvm_pipeline_result[_raw],
+ * tvm_pipeline_vulns (grp_recs numbered per member), tvm_pipeline_filter_stats and
+ * tvm_vuln_set_walk on tvm_group_batch_member(gb, k) / tvm_group_engine(g, k); taken in member
+ * order they are the batch's rows in batch order.  The index width is each member's own. */
+int tvm_group_pipeline_prepare(tvm_group_batch* gb, uint64_t match_cap, const uint64_t* member_caps,
+                               uint32_t chunk_packages, uint32_t flags, char* err, size_t errlen);
+int tvm_group_pipeline_set_filter(tvm_group_batch* gb, const tvm_filter_opts* o, char* err, size_t errlen);
+int tvm_group_pipeline_run(tvm_group_batch* gb, uint64_t* n_matches, int64_t* err_pkg, double* ms,
+                           uint64_t* member_matches, char* err, size_t errlen);
+
+/* The device-resident pass over a group: tvm_batch_upload / tvm_match_launch (asynchronous, on
+ * every member) / tvm_match_status (sums; member_matches NULL or size entries; *err_pkg global). */
+int tvm_group_upload(tvm_group_batch* gb, uint64_t match_cap, const uint64_t* member_caps, char* err, size_t errlen);
+int tvm_group_launch(tvm_group_batch* gb, char* err, size_t errlen);
+int tvm_group_status(tvm_group_batch* gb, uint64_t* n_matches, int64_t* err_pkg, uint64_t* err_bits,
+                     uint64_t* member_matches);
+/* The whole batch's per-package advisory lists in batch order, in caller-owned buffers on member
+ * root's device (tvm_match_order_into's layout over all packages: csr_adv[row_end[p-1] ..
+ * row_end[p]), row_end[-1] = 0; cap entries of csr_adv, one row end per package).  Each member
+ * orders its list on its own device with its row ends rebased by the matches of the members
+ * before it, then its two arrays are copied into place (a device copy on the root's device, a
+ * peer copy otherwise; no kernel writes another device's memory) and every member is
+ * synchronised, the root last.  TVM_EINVAL with *n_out = the total when the total reaches 2^31
+ * (row ends are 32-bit) or exceeds cap, after an overflowed member pass, and for a merged list
+ * (as tvm_match_order_into).  An empty shard contributes nothing. */
+int tvm_group_csr_into(tvm_group_batch* gb, int root, void* csr_adv_dev, void* row_end_dev, uint64_t cap,
+                       uint64_t* n_out, char* err, size_t errlen);
+
 #ifdef __cplusplus
 }
 #endif

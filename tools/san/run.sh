@@ -5,7 +5,7 @@
 #   2. libFuzzer + ASan + UBSan over the untrusted-input decoders (CycloneDX, bbolt), seeded
 #      from the reference's own SBOM / bolt fixtures (tests/golden)
 #   3. TSan: the worker pool, the parallel wire encoder and the SBOM decoder's host threads,
-#      1 thread against 8 (tools/san/tsan_host.cpp)
+#      1 thread against 8, and an engine group's member threads (tools/san/tsan_host.cpp)
 # Logs: profiles/r06/san/ (OUT=...).  The fuzzers are built without ASan's global-variable
 # instrumentation (-asan-globals=0): with -fsanitize=fuzzer this clang registers identical
 # string literals of one module twice and aborts on a false "ODR violation / misaligned global"

@@ -3,7 +3,10 @@
 // 1 thread, byte for byte; (2) the process-wide WorkerPool (host_par.h) driven by two caller
 // threads at once (jobs serialise on the pool), then shut down (tvm_shutdown's path) with a job
 // after it running inline; (3) the CycloneDX decoder's parallel pieces (sbom.cpp) at 8 threads
-// against 1.  Exit 0 = every comparison equal (TSan halts on the first race).
+// against 1; (4) an engine group's member threads (host_par.h LaneThreads) driven by two callers
+// at once over three lanes, stopped (tvm_group_close / tvm_shutdown's path, twice), with a run
+// after the stop staying on the caller.  Exit 0 = every comparison equal (TSan halts on the
+// first race).
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -105,6 +108,37 @@ int main() {
   }
   if (dumps[0].empty() || dumps[0] != dumps[1]) return fail("sbom decode: 8 threads differ from 1");
   std::printf("sbom decode: %zu bytes of text, 1 == 8 threads\n", doc.size());
+
+  // (4) the member threads of an engine group: two callers at once, overlapping lane sets
+  {
+    LaneThreads lanes(3);
+    std::atomic<int> wrong{0};
+    auto group_caller = [&](int seed, std::vector<int> ks) {
+      for (int pass = 0; pass < 300; pass++) {
+        std::vector<uint64_t> out(3, 0);
+        std::vector<std::thread::id> who(3);
+        lanes.run(ks, [&](int k) {
+          out[size_t(k)] = uint64_t(seed) * 1000 + uint64_t(pass) * 3 + uint64_t(k);
+          who[size_t(k)] = std::this_thread::get_id();
+        });
+        for (int k : ks)
+          if (out[size_t(k)] != uint64_t(seed) * 1000 + uint64_t(pass) * 3 + uint64_t(k)) wrong++;
+        if (who[size_t(ks[0])] != std::this_thread::get_id()) wrong++;  // the first lane is the caller's
+      }
+    };
+    std::thread c1(group_caller, 1, std::vector<int>{0, 1, 2}), c2(group_caller, 2, std::vector<int>{1, 2}),
+        c3(group_caller, 3, std::vector<int>{2});
+    c1.join();
+    c2.join();
+    c3.join();
+    if (wrong) return fail("lane threads: wrong results");
+    lanes.stop();
+    lanes.stop();
+    int inline_runs = 0;  // no lock: after stop() every lane runs on the caller
+    lanes.run({0, 1, 2}, [&](int) { inline_runs++; });
+    if (inline_runs != 3) return fail("lane threads after stop");
+    std::printf("lane threads: 3 callers x 300 passes over 3 lanes, stop twice, inline run: ok\n");
+  }
   std::printf("tsan harness: ok\n");
   return 0;
 }

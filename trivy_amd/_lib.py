@@ -284,6 +284,35 @@ _SIG = [
                                              ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_pipeline_set_filter", ctypes.c_int, [_P, _P, ctypes.POINTER(FilterOpts), ctypes.c_char_p, ctypes.c_size_t]),
     ("tvm_pipeline_filter_stats", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    # in-process multi-device: engine groups
+    ("tvm_group_open", _P, [_P, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
+    ("tvm_group_close", None, [_P]),
+    ("tvm_group_size", ctypes.c_int, [_P]),
+    ("tvm_group_engine", _P, [_P, ctypes.c_int]),
+    ("tvm_group_swap", ctypes.c_int, [_P, _P, ctypes.c_char_p, ctypes.c_size_t]),
+    ("tvm_group_plan_host", ctypes.c_int, [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_void_p]),
+    ("tvm_group_batch_new", _P, [_P]),
+    ("tvm_group_batch_free", None, [_P]),
+    ("tvm_group_batch_cpe_set", ctypes.c_int64, [_P, ctypes.c_void_p, ctypes.c_size_t, Str]),
+    ("tvm_group_batch_add_targets", ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(Str),
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tvm_group_batch_size", ctypes.c_int64, [_P]),
+    ("tvm_group_batch_shards", ctypes.c_int, [_P, ctypes.c_void_p]),
+    ("tvm_group_batch_member", _P, [_P, ctypes.c_int]),
+    ("tvm_group_pipeline_prepare", ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                                  ctypes.c_char_p, ctypes.c_size_t]),
+    ("tvm_group_pipeline_set_filter", ctypes.c_int, [_P, ctypes.POINTER(FilterOpts), ctypes.c_char_p, ctypes.c_size_t]),
+    ("tvm_group_pipeline_run", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_char_p,
+                                              ctypes.c_size_t]),
+    ("tvm_group_upload", ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]),
+    ("tvm_group_launch", ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_size_t]),
+    ("tvm_group_status", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]),
+    ("tvm_group_csr_into", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                          ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p, ctypes.c_size_t]),
 ]
 
 EXPORTED = [s[0] for s in _SIG]

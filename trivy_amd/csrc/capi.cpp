@@ -24,6 +24,7 @@
 #include "libdb.h"
 #include "libver.h"
 #include "bbolt.h"
+#include "capi_hooks.h"
 #include "host_par.h"
 #include "pipeline.h"
 #include "pool.h"
@@ -444,6 +445,7 @@ void tvm_shutdown(void) {
   for (int d = 0; d < 64; d++)
     if ((used >> d) & 1u)
       if (hipSetDevice(d) == hipSuccess) (void)hipDeviceSynchronize();
+  capi_hooks::shutdown_groups();  // the member threads of every live engine group
   WorkerPool::shutdown_all();
   release_encoders();
   pool_close();
@@ -465,20 +467,36 @@ int tvm_device_sync(int device, char* err, size_t errlen) {
   return TVM_OK;
 }
 
-int tvm_engine_swap(tvm_engine* e, tvm_db* db, char* err, size_t errlen) {
-  if (!e || !db || !db->finalized) return TVM_EINVAL;
-  std::string msg;
-  Engine* fresh = Engine::open(db->db, e->device, msg);  // build before quiescing
-  FillEngine* fresh_fill = fresh ? FillEngine::open(db->vt, e->device, msg) : nullptr;
-  if (!fresh || !fresh_fill) {
-    delete fresh;
-    set_err(err, errlen, msg);
-    return TVM_EDEVICE;
-  }
+}  // extern "C"
+
+// tvm_engine_swap in its two steps, for a caller that swaps several engines as one
+// (group.cpp tvm_group_swap: every member's tables are built before any member is swapped).
+namespace tvm {
+namespace capi_hooks {
+
+bool swap_build(tvm_engine* e, tvm_db* db, SwapTables& out, std::string& msg) {
+  out.eng = Engine::open(db->db, e->device, msg);  // build before quiescing
+  out.fill = out.eng ? FillEngine::open(db->vt, e->device, msg) : nullptr;
+  if (out.eng && out.fill) return true;
+  swap_discard(e, out);
+  return false;
+}
+
+void swap_discard(tvm_engine* e, SwapTables& t) {
+  (void)hipSetDevice(e->device);
+  delete t.fill;
+  delete t.eng;
+  t.eng = nullptr;
+  t.fill = nullptr;
+}
+
+void swap_commit(tvm_engine* e, tvm_db* db, SwapTables& t) {
   std::unique_lock<std::shared_mutex> lk(e->mu);
   (void)hipSetDevice(e->device);
-  e->eng.reset(fresh);  // ~Engine drains its streams before it frees the tables
-  e->fill.reset(fresh_fill);
+  e->eng.reset(t.eng);  // ~Engine drains its streams before it frees the tables
+  e->fill.reset(t.fill);
+  t.eng = nullptr;
+  t.fill = nullptr;
   e->db = db;
   e->gen++;
   if (e->rh_rank) {
@@ -489,6 +507,29 @@ int tvm_engine_swap(tvm_engine* e, tvm_db* db, char* err, size_t errlen) {
     (void)hipFree(e->cls);
     e->cls = nullptr;
   }
+}
+
+int engine_device(const tvm_engine* e) { return e->device; }
+void with_engine_db(tvm_engine* e, const std::function<void(const tvm_db*)>& f) {
+  std::shared_lock<std::shared_mutex> lk(e->mu);
+  f(e->db);
+}
+bool db_finalized(const tvm_db* db) { return db && db->finalized; }
+
+}  // namespace capi_hooks
+}  // namespace tvm
+
+extern "C" {
+
+int tvm_engine_swap(tvm_engine* e, tvm_db* db, char* err, size_t errlen) {
+  if (!e || !db || !db->finalized) return TVM_EINVAL;
+  std::string msg;
+  capi_hooks::SwapTables t;
+  if (!capi_hooks::swap_build(e, db, t, msg)) {
+    set_err(err, errlen, msg);
+    return TVM_EDEVICE;
+  }
+  capi_hooks::swap_commit(e, db, t);
   return TVM_OK;
 }
 
@@ -995,12 +1036,21 @@ int tvm_match_copy_device(tvm_engine* e, tvm_batch* b, void* dst, uint64_t cap, 
   return TVM_OK;
 }
 
-int tvm_match_order_into(tvm_engine* e, tvm_batch* b, void* csr_adv_dev, void* row_end_dev, uint64_t cap,
-                         uint64_t* n_out, char* err, size_t errlen) {
-  uint64_t n = 0;
-  int rc = tvm_match_status(e, b, &n, nullptr, nullptr);
-  if (rc) return rc;
-  if (n_out) *n_out = n;
+}  // extern "C"
+
+namespace tvm {
+namespace capi_hooks {
+
+void pipeline_drop(tvm_batch* b) {
+  b->pipe.reset();
+  b->pipe_total = b->pipe_kept = 0;
+  b->pipe_ok = false;
+}
+
+int order_refusal(const tvm_batch* b, uint64_t n) { return (b->merged || n > b->m.cap) ? TVM_EINVAL : TVM_OK; }
+
+int order_into(tvm_engine* e, tvm_batch* b, void* csr_adv_dev, void* row_end_dev, uint64_t cap, uint64_t n,
+               uint32_t row_base, bool sync, char* err, size_t errlen) {
   if (b->merged || n > b->m.cap || n > cap || !row_end_dev || (n && !csr_adv_dev)) return TVM_EINVAL;
   std::shared_lock<std::shared_mutex> lk(e->mu);
   if (!bind(b, e)) {
@@ -1035,15 +1085,47 @@ int tvm_match_order_into(tvm_engine* e, tvm_batch* b, void* csr_adv_dev, void* r
   oa.t0 = 0;
   oa.n = b->dev.n;
   oa.pkg_base = b->dev.pkg_base;
+  oa.row_base = row_base;
   if (hipMemsetAsync(b->order_scratch, 0, size_t(nt + 1) * 8, st) != hipSuccess) return TVM_EDEVICE;
   launch_order(nt, st, oa);
   const hipError_t le = hipGetLastError();
-  const hipError_t se = le == hipSuccess ? hipStreamSynchronize(st) : le;
+  const hipError_t se = (le == hipSuccess && sync) ? hipStreamSynchronize(st) : le;
   if (se != hipSuccess) {
     set_err(err, errlen, std::string("order kernel: ") + hipGetErrorString(se));
     return TVM_EDEVICE;
   }
   return TVM_OK;
+}
+
+int copy_from_engine(tvm_engine* e, void* dst, int dst_device, const void* src, size_t bytes, char* err,
+                     size_t errlen) {
+  if (bytes == 0) return TVM_OK;
+  std::shared_lock<std::shared_mutex> lk(e->mu);
+  (void)hipSetDevice(e->device);
+  hipStream_t st = e->eng->stream();
+  const hipError_t rc = dst_device == e->device
+                            ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st)
+                            : hipMemcpyPeerAsync(dst, dst_device, src, e->device, bytes, st);
+  if (rc != hipSuccess) {
+    set_err(err, errlen, std::string(dst_device == e->device ? "hipMemcpyAsync: " : "hipMemcpyPeerAsync: ") +
+                             hipGetErrorString(rc));
+    return TVM_EDEVICE;
+  }
+  return TVM_OK;
+}
+
+}  // namespace capi_hooks
+}  // namespace tvm
+
+extern "C" {
+
+int tvm_match_order_into(tvm_engine* e, tvm_batch* b, void* csr_adv_dev, void* row_end_dev, uint64_t cap,
+                         uint64_t* n_out, char* err, size_t errlen) {
+  uint64_t n = 0;
+  int rc = tvm_match_status(e, b, &n, nullptr, nullptr);
+  if (rc) return rc;
+  if (n_out) *n_out = n;
+  return capi_hooks::order_into(e, b, csr_adv_dev, row_end_dev, cap, n, 0, true, err, errlen);
 }
 
 int tvm_match_time(tvm_engine* e, tvm_batch* b, int steps, double* ms, char* err, size_t errlen) {

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <utility>
@@ -160,6 +161,104 @@ class WorkerPool {
   int busy_ = 0;
   uint64_t gen_ = 0;
   bool stop_ = false, stopped_ = false;
+};
+
+// One parked thread per lane 1..n-1 (lane 0 has none) for calls that fan out over fixed lanes:
+// an engine group's members, each of which keeps its own host thread for the length of a pass.
+// run(lanes, f) calls f(lane) for every listed lane - the first on the caller, each other on
+// its lane's thread - and returns when all have.  Several callers may run at once: a lane's
+// jobs are served in arrival order.  stop() serves what is queued, then joins the threads
+// (idempotent; the owner's destructor and tvm_shutdown call it); later runs stay on the caller.
+// No thread is ever detached.
+class LaneThreads {
+ public:
+  explicit LaneThreads(int lanes) {
+    for (int i = 1; i < lanes; i++) q_.emplace_back(new Lane());
+    for (auto& l : q_) l->th = std::thread([p = l.get()] { loop(*p); });
+  }
+  ~LaneThreads() { stop(); }
+  LaneThreads(const LaneThreads&) = delete;
+  LaneThreads& operator=(const LaneThreads&) = delete;
+  // lanes: ascending, distinct, each below the lane count
+  void run(const std::vector<int>& lanes, const std::function<void(int)>& f) {
+    if (lanes.empty()) return;
+    Latch done;
+    bool handed = false;
+    {
+      std::lock_guard<std::mutex> g(submit_mu_);
+      if (!stopped_ && lanes.size() > 1) {
+        handed = true;
+        done.pending = int(lanes.size()) - 1;
+        for (size_t i = 1; i < lanes.size(); i++) {
+          Lane& l = *q_[size_t(lanes[i]) - 1];
+          {
+            std::lock_guard<std::mutex> lk(l.mu);
+            l.jobs.push_back(Job{&f, lanes[i], &done});
+          }
+          l.cv.notify_one();
+        }
+      }
+    }
+    f(lanes[0]);
+    if (!handed) {
+      for (size_t i = 1; i < lanes.size(); i++) f(lanes[i]);
+      return;
+    }
+    std::unique_lock<std::mutex> lk(done.mu);
+    done.cv.wait(lk, [&] { return done.pending == 0; });
+  }
+  void stop() {
+    std::lock_guard<std::mutex> g(submit_mu_);  // no run() is handing jobs out
+    if (stopped_) return;
+    stopped_ = true;
+    for (auto& l : q_) {
+      {
+        std::lock_guard<std::mutex> lk(l->mu);
+        l->stop = true;
+      }
+      l->cv.notify_one();
+    }
+    for (auto& l : q_) l->th.join();
+  }
+  int threads() const { return int(q_.size()); }
+
+ private:
+  struct Latch {
+    std::mutex mu;
+    std::condition_variable cv;
+    int pending = 0;
+  };
+  struct Job {
+    const std::function<void(int)>* f;
+    int lane;
+    Latch* done;
+  };
+  struct Lane {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<Job> jobs;
+    bool stop = false;
+    std::thread th;
+  };
+  static void loop(Lane& l) {
+    for (;;) {
+      Job j;
+      {
+        std::unique_lock<std::mutex> lk(l.mu);
+        l.cv.wait(lk, [&] { return l.stop || !l.jobs.empty(); });
+        if (l.jobs.empty()) return;  // stop, and nothing left to serve
+        j = l.jobs.front();
+        l.jobs.erase(l.jobs.begin());
+      }
+      (*j.f)(j.lane);
+      // the waiter may leave (and destroy the latch) as soon as pending is 0: notify under its lock
+      std::lock_guard<std::mutex> lk(j.done->mu);
+      if (--j.done->pending == 0) j.done->cv.notify_one();
+    }
+  }
+  std::vector<std::unique_ptr<Lane>> q_;
+  std::mutex submit_mu_;
+  bool stopped_ = false;
 };
 
 // range_for on the parked WorkerPool threads (no thread start per call: the batch export's

@@ -10,7 +10,9 @@
 // global offset with hardly any waiting, and the tile copies its segment there.  Tiles take
 // tickets, so a tile only ever waits on tiles that started before it.  Chunks of a
 // pipelined pass run in order on one stream, so a chunk's first tile looks back into the
-// previous chunk's (finished) tiles: offsets are global across chunks.
+// previous chunk's (finished) tiles: offsets are global across chunks.  OrderArgs::row_base is
+// added to the row ends alone: a shard of an engine group (group.cpp) stores row ends that
+// already count the list entries of the shards before it, so a copy puts them into the union.
 #include "pipeline.h"
 
 namespace tvm {
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(kTile) void order_kernel(OrderArgs a) {
 #pragma unroll
   for (int w = 0; w < kTile / 64; w++) off += (uint32_t(w) < wave) ? wsum[w] : 0u;
   const uint32_t p = p_first + tid;
-  if (p < a.n) a.row_end[p] = uint32_t(b + off + x);
+  if (p < a.n) a.row_end[p] = uint32_t(b + off + x) + a.row_base;
 }
 
 __global__ __launch_bounds__(kTile) void copy_out_kernel(CopyOutArgs a) {

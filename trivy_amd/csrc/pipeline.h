@@ -21,6 +21,8 @@ struct OrderArgs {
   uint32_t t0;                 // first tile of this launch
   uint32_t n;                  // packages in the batch
   uint32_t pkg_base = 0;       // added to every package index the match kernels wrote (a shard's first package)
+  uint32_t row_base = 0;       // added to every row end stored (the list entries of the shards before this one;
+                               // csr_adv positions and cap stay the shard's own)
 };
 void launch_order(uint32_t n_tiles, hipStream_t st, const OrderArgs& a);
 void launch_copy_out(hipStream_t st, const CopyOutArgs& a);  // engine.h copy_out_tiles as its own kernel
