@@ -184,9 +184,10 @@ __device__ __forceinline__ uint64_t name_word(const P* base, uint32_t sh, uint32
 // Hash of (plat, name) from the name's bytes, word by word.
 template <class P>
 __device__ __forceinline__ uint64_t name_hash(uint32_t plat, const uint8_t* s, uint32_t n) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(s);
-  const P* base = reinterpret_cast<const P*>(a & ~uintptr_t(3));
-  const uint32_t sh = uint32_t(a & 3);
+  // the aligned base is taken from s by subtraction, not through an integer: the compiler then
+  // still knows s's address space, and a staged name is read with ds_read, not a flat load
+  const uint32_t sh = uint32_t(reinterpret_cast<uintptr_t>(s)) & 3u;
+  const P* base = reinterpret_cast<const P*>(s - sh);
   uint64_t h = key_hash_seed2(plat, n);
   for (uint32_t i = 0; 8 * i < n; i++) h = key_hash_word(h, name_word(base, sh, i, n));
   return key_hash_fin(h);
@@ -199,9 +200,8 @@ template <class P>
 __device__ __forceinline__ bool name_eq_slot(const uint8_t* s, uint32_t n, const uint4 q1, const uint4 q2,
                                              const uint4 q3, const uint8_t* arena) {
   static_assert(kSlotNameWords == 4, "four inline name words (q3.z / q3.w: Slot::pfx)");
-  const uintptr_t a = reinterpret_cast<uintptr_t>(s);
-  const P* base = reinterpret_cast<const P*>(a & ~uintptr_t(3));
-  const uint32_t sh = uint32_t(a & 3);
+  const uint32_t sh = uint32_t(reinterpret_cast<uintptr_t>(s)) & 3u;  // as name_hash: s's address space is kept
+  const P* base = reinterpret_cast<const P*>(s - sh);
   const uint64_t y[kSlotNameWords] = {q1.z | (uint64_t(q1.w) << 32), q2.x | (uint64_t(q2.y) << 32),
                                       q2.z | (uint64_t(q2.w) << 32), q3.x | (uint64_t(q3.y) << 32)};
   bool eq = true;
@@ -250,12 +250,14 @@ __device__ __forceinline__ bool fp_chain(const ProbeArgs& a, uint64_t h, uint64_
 
 // What the balanced kernel (fused_kernel, SEG bit 5) has of a package before probe_one runs: the
 // name's hash, the fingerprint walk's outcome and the slot heads, and deb_fast_key's outcome and key
-// length, with the key already in the lane's LDS slot (PRE = 2).
+// length, with the key already in the lane's LDS slot (PRE = 2); PRE = 3: the platform's descriptor
+// too, loaded ahead of the slot heads, so that nothing behind the heads is waited for before them.
 struct ProbePre {
   uint64_t h, start;
   uint4 q0, q0n;
   bool found, has_q0n;
   uint32_t fast_st, fast_kl;
+  PlatInfo pi;
 };
 
 // One package: encode, hash, probe.  P = uint32_t in the LDS or global address space of s.
@@ -265,7 +267,9 @@ __device__ __forceinline__ void probe_one(const ProbeArgs& a, uint32_t p, uint32
                                           const uint8_t* name, const uint8_t* ver, uint64_t vglob, PkgRec& r,
                                           uint8_t* kb = nullptr, const uint8_t* tab = nullptr,
                                           const ProbePre* pre = nullptr) {
-  const PlatInfo pi = a.db.plats[plat];
+  PlatInfo pi;
+  if constexpr (PRE == 3) pi = pre->pi;
+  else pi = a.db.plats[plat];
   // the hash and the fingerprint walk come before the encoder; the dpkg-only kernels load the
   // slot heads before it too, the other grammar sets after it (their encoders' registers: held
   // across them, the heads made the all-grammar kernel spill)
@@ -302,7 +306,7 @@ __device__ __forceinline__ void probe_one(const ProbeArgs& a, uint32_t p, uint32
   if (!(DIAG & 1) && kb && ((GM >> CMP_DEB) & 1u) && pi.cmp == CMP_DEB) {
     uint32_t kl = 0, st;
     // DIAG bit 3 (measurement only): the encoder sees at most 12 version bytes, 3 dword trips
-    if constexpr (PRE == 2) {
+    if constexpr (PRE >= 2) {
       st = pre->fast_st;
       kl = pre->fast_kl;
     } else {
@@ -1191,6 +1195,14 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
   // whose name is absent gets no key and no rows.
   constexpr bool kBal = (SEG & 32) != 0;
   static_assert(!kBal || (GM == GM_DEB && (SEG & 2) && DIAG == 0), "encoder balance: dpkg-only, per-wave staging");
+  // The slot heads of a listed lane stay in flight across the list entry, both barriers and the packed
+  // encode, up to probe_one's first use of them: the lane's platform descriptor is loaded behind the
+  // window and waited for with it, ahead of the hash, so nothing issued behind the heads is waited for
+  // before them, and the staged strings are read with LDS instructions, which do not count on vmcnt.
+  // kHeadWait (SEG bit 6; the A/B partner, fused_k4_m2400_wseg_rec_hw_r16): the form before that - the
+  // descriptor's grammar byte loaded behind the heads and waited for at the list entry, heads included.
+  constexpr bool kHeadWait = (SEG & 64) != 0;
+  static_assert(!kHeadWait || kBal, "SEG bit 6 is a form of the balanced kernel");
   struct ProbePart {
     uint32_t kbuf[kTile * kFastKeyStride / 4];
     uint8_t tab[128];
@@ -1282,14 +1294,29 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
   ProbePre pre;  // kBal
   pre.h = pre.start = 0;
   pre.q0 = pre.q0n = make_uint4(0, 0, 0, 0);
+  if constexpr (kBal && !kHeadWait) {
+    // any value: the heads are read only behind `found` / `has_q0n`.  Zeros made the loaded head
+    // a copy into the zeroed registers where the branches join, and the copy waited for the load.
+    uint32_t any;
+    asm volatile("" : "=v"(any));
+    pre.q0 = pre.q0n = make_uint4(any, any, any, any);
+  }
   pre.found = pre.has_q0n = false;
   pre.fast_st = pre.fast_kl = 0;
+  pre.pi = PlatInfo{};
+  // through a clamped index and a select, as the package words: under `own` the load was waited
+  // for inside the branch with vmcnt(0), the window's loads with it (entry 0 is always allocated)
+  if constexpr (kBal && !kHeadWait) pre.pi = a.db.plats[d.x < a.db.n_plats ? d.x : 0u];
   bool listed = false;
   if constexpr (kWaveStage) {
     off = wave_exscan(nlen + vlen, tid & 63);
     sbuf = buf + (tid >> 6) * (STG / 4 / 16 + 2);
     window_store<kSV, kSW, false>(sbuf, wv, nv, tid & 63);
     if (tid < 128) u.pr.tab[tid] = deb_fast_code(tid);
+    // the descriptor is waited for here, behind the window it was issued behind, on every path:
+    // left pending on the path of an unstaged window (which never reads it), it was waited for
+    // at probe_one's first read of it, behind both barriers - with vmcnt(0), the heads included
+    if constexpr (kBal && !kHeadWait) asm volatile("" ::"v"(pre.pi.flags), "v"(uint32_t(pre.pi.cmp)));
     if constexpr (kBal) {
       if (!staged) {
         if ((tid & 63) == 0) u.pr.bal_mixed = 1;
@@ -1302,7 +1329,8 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
           pre.q0 = slot_head(a, pre.start);
           pre.has_q0n = !(pre.start & 1);
           if (pre.has_q0n) pre.q0n = slot_head(a, pre.start + 1);
-          listed = a.db.plats[d.x].cmp == CMP_DEB;
+          if constexpr (kHeadWait) listed = a.db.plats[d.x].cmp == CMP_DEB;
+          else listed = pre.pi.cmp == CMP_DEB;
           if (listed) {
             const uint32_t b = enc_bal_bucket(vlen);
             const uint32_t rank = atomicAdd(&u.pr.bal_cnt[b], 1u);  // < kTile: a lane enters at most once
@@ -1345,8 +1373,8 @@ __global__ __launch_bounds__(kTile, WPE) void fused_kernel(FusedArgs fa) {
       const uint32_t w = reinterpret_cast<const uint32_t*>(kbytes + tid * kFastKeyStride)[10];
       pre.fast_st = w & 0xFFu;
       pre.fast_kl = w >> 8;
-      probe_one<GM, uint32_t, 0, 2>(a, p, d.x, nlen, vlen, sb, sb + nlen, w0 + off + nlen, r,
-                                    kbytes + tid * kFastKeyStride, u.pr.tab, &pre);
+      probe_one<GM, uint32_t, 0, kHeadWait ? 2 : 3>(a, p, d.x, nlen, vlen, sb, sb + nlen, w0 + off + nlen, r,
+                                                    kbytes + tid * kFastKeyStride, u.pr.tab, &pre);
     } else if (own && (!packed || pre.found)) {
       // rare: lane per package, as without the list - a tile with a window that is not staged, or
       // a platform of another grammar (an absent name of a packed tile: no key, no rows)
@@ -1403,8 +1431,8 @@ void launch_fused(uint32_t n_tiles, hipStream_t st, const FusedArgs& a) {
 // (match_variants.h: F = 0 split, 1-3 fused, 4 fused with per-wave sweep segments, 5 also
 // per-wave staging, 6 the same held at 6 waves, 7 per-wave staging + segments over the hot rows
 // (DB::rows16, dpkg-only), 8 the same with rank-indexed windows and the one-compare pair test, 9
-// that kernel with the tile's encoder work list (fused_kernel kBal), 11-15, 25-26 and 28 fused
-// measurement builds).
+// that kernel with the tile's encoder work list (fused_kernel kBal), 20 the same with the slot heads
+// waited for at the list entry (kHeadWait), 11-15, 25-26 and 28 fused measurement builds).
 template <uint32_t GM, int FILT, int F, int K, int MB>
 constexpr FusedFn fused_entry() {
   if constexpr (F == 0) return nullptr;
@@ -1419,6 +1447,9 @@ constexpr FusedFn fused_entry() {
     else return nullptr;
   } else if constexpr (F == 9) {  // F = 8 with the tile's encoder work list (fused_kernel kBal)
     if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | 12 | 16 | 32>;
+    else return nullptr;
+  } else if constexpr (F == 20) {  // F = 9 with the slot heads waited for at the list entry (fused_kernel kHeadWait)
+    if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | 12 | 16 | 32 | 64>;
     else return nullptr;
   } else if constexpr (F == 25 || F == 26) {  // TVM_DIAG: 16-byte row loads, dpkg-only
     if constexpr (GM == GM_DEB) return &launch_fused<GM, K, MB, FILT, 0, 1, 3 | (F == 25 ? 4 : 8)>;

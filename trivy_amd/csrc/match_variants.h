@@ -18,7 +18,8 @@
   X(7, 4, 2400, "fused_k4_m2400_wseg_r16") \
   X(7, 8, 2400, "fused_k8_m2400_wseg_r16") \
   X(8, 4, 2400, "fused_k4_m2400_wseg_rec_lane_r16") \
-  X(9, 4, 2400, "fused_k4_m2400_wseg_rec_r16")
+  X(9, 4, 2400, "fused_k4_m2400_wseg_rec_r16") \
+  X(20, 4, 2400, "fused_k4_m2400_wseg_rec_hw_r16")
 
 // Measurement-only variants (wrong match lists by construction): built only with
 // `make DIAG=1` (-DTVM_DIAG), never reachable in the product library.
@@ -69,6 +70,11 @@ constexpr int kNumTuned = 0 TVM_MATCH_VARIANTS(TVM_VARIANT_COUNT_);
 // Since the tile's encoder work list (fused_kernel kBal, F = 9; C2 sweep, profiles/encbal/sweep_c2.txt):
 // that kernel carries the name fused_k4_m2400_wseg_rec_r16, and the kernel that encodes lane per
 // package (F = 8, auto until then) stays in the list as fused_k4_m2400_wseg_rec_lane_r16, its A/B partner.
+// Since the staged strings are read with LDS instructions and a listed lane's slot heads stay in flight
+// across the list entry, both barriers and the packed encode (C2, profiles/ldsread/: 0.3549 -> 0.3315 ms
+// alternated with the parent commit; in one process 0.3190 ms against 0.3268): still F = 9 under its name;
+// the form that waits for the heads at the list entry is appended as fused_k4_m2400_wseg_rec_hw_r16
+// (F = 20), its A/B partner, so the indices before it and kAutoVariant stay what they were.
 constexpr int kAutoVariant = 12;         // fused_k4_m2400_wseg_rec_r16
 constexpr int kAutoVariantFiltered = 1;  // fused_k2_m2048
 // OS grammar sets with row filters (rpm / apk: no library rows): per-wave staging + segments

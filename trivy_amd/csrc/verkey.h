@@ -363,9 +363,11 @@ TVM_HD void deb_fast_byte(uint32_t c, bool split, uint8_t* kb, const uint8_t* ta
 // Key of dpkg version s[0, n) into kb[0, len) (kb: kFastKeyStride writable bytes).
 // Returns FAST_OK, FAST_INVALID (go-deb-version NewVersion error) or FAST_FALLBACK.
 TVM_HD uint32_t deb_fast_key(const uint8_t* s, uint32_t n, uint8_t* kb, const uint8_t* tab, uint32_t& len) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(s);
-  const uint32_t* base = reinterpret_cast<const uint32_t*>(a & ~uintptr_t(3));
-  const uint32_t sh = uint32_t(a & 3);
+  // the aligned dword that holds s[0], reached from s by subtraction and not through an integer:
+  // on the device s then keeps its address space, and a staged version is read with ds_read
+  // (a pointer rebuilt from an integer is generic: flat loads, which wait on vmcnt as well)
+  const uint32_t sh = uint32_t(reinterpret_cast<uintptr_t>(s)) & 3u;
+  const uint32_t* base = reinterpret_cast<const uint32_t*>(s - sh);
   // pre-pass: first and last ':', last '-', any byte >= 0x80
   uint32_t colon = n, lcolon = n, dash = n, high = 0;
   for (uint32_t j = 0; j < n; j += 4) {
@@ -409,9 +411,8 @@ TVM_HD uint32_t deb_fast_key(const uint8_t* s, uint32_t n, uint8_t* kb, const ui
   DebFastState st{pos, 0u, false, false, false};
   const uint8_t* s2 = s + r0;
   const uint32_t m = n - r0, sp2 = has_rev ? dash - r0 : 0xFFFFFFFFu;
-  const uintptr_t a2 = reinterpret_cast<uintptr_t>(s2);
-  const uint32_t* base2 = reinterpret_cast<const uint32_t*>(a2 & ~uintptr_t(3));
-  const uint32_t sh2 = uint32_t(a2 & 3);
+  const uint32_t sh2 = uint32_t(reinterpret_cast<uintptr_t>(s2)) & 3u;
+  const uint32_t* base2 = reinterpret_cast<const uint32_t*>(s2 - sh2);
   for (uint32_t j = 0; j + 4 <= m; j += 4) {
     const uint32_t x = str_dword(base2, sh2, j >> 2);
 #pragma unroll
