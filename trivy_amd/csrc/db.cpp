@@ -582,6 +582,15 @@ static void set_head(Row& r, const std::vector<uint8_t>& kb, bool h24) {
   for (size_t i = 0; i < kb.size() && i < (h24 ? 24u : 16u); i++) *w[i / 8] |= uint64_t(kb[i]) << (8 * (7 - i % 8));
 }
 
+// A bound whose sort key does not fit the rows' 14-bit length fields (KEY_LEN_MASK): the row
+// would compare a wrapped length, silently.  The first such advisory is remembered and
+// finalize() fails with it.
+void DB::note_long_key(const Platform& P, const Advisory& a, size_t n) {
+  if (long_key_err_.empty())
+    long_key_err_ = "advisory " + a.vuln_id + " of bucket \"" + P.name + "\": a version bound with a sort key of " +
+                    std::to_string(n) + " bytes (limit " + std::to_string(unsigned(KEY_LEN_MASK)) + ") cannot be compared";
+}
+
 // Advisory -> interval row(s) of its driver (SURVEY.md §8a' "unfixed" and parse-error
 // columns).  Returns false when the advisory can never be reported (no row).
 bool DB::compile_rows(const Platform& P, const Advisory& a, uint32_t ai, std::vector<uint8_t>& kb) {
@@ -649,6 +658,7 @@ bool DB::compile_rows(const Platform& P, const Advisory& a, uint32_t ai, std::ve
       auto put = [&](const KBound& b, uint32_t& off, uint16_t& len, bool hi) {
         if (b.inf) return;
         kb.assign(b.k.begin(), b.k.end());
+        if (kb.size() > KEY_LEN_MASK) note_long_key(P, a, kb.size());
         off = intern_key(kb);
         len = uint16_t(std::min<size_t>(kb.size(), KEY_LEN_MASK) | (b.incl ? KEY_INCL : 0));
         if (hi) set_head(r, kb, false);
@@ -678,8 +688,9 @@ bool DB::compile_rows(const Platform& P, const Advisory& a, uint32_t ai, std::ve
     kb.clear();
     VecSink s{&kb};
     if (!encode_version(P.cmp, reinterpret_cast<const uint8_t*>(v.data()), uint32_t(v.size()), s)) return false;
+    if (kb.size() > KEY_LEN_MASK) note_long_key(P, a, kb.size());
     off = intern_key(kb);
-    len = uint16_t(kb.size());
+    len = uint16_t(kb.size() & KEY_LEN_MASK);
     return true;
   };
   auto set_hi = [&](const std::string& v) {
@@ -1063,7 +1074,12 @@ bool DB::finalize(std::string& err) {
     }
   }
   if (advs.size() >= ROW_ADV_MASK) { err = "too many advisories"; return false; }
+  long_key_err_.clear();
   build_index();
+  if (!long_key_err_.empty()) {
+    err = long_key_err_;
+    return false;
+  }
   return true;
 }
 

@@ -144,6 +144,8 @@ class DB {
   void flatten_os(uint32_t plat, const Bucket& b, int32_t ds);
   void flatten_library(uint32_t plat, const std::vector<std::pair<const Bucket*, int32_t>>& roots);
   bool compile_rows(const Platform& P, const Advisory& a, uint32_t ai, std::vector<uint8_t>& kb);
+  void note_long_key(const Platform& P, const Advisory& a, size_t n);
+  std::string long_key_err_;  // the first bound key over KEY_LEN_MASK bytes (finalize fails with it)
   static constexpr uint32_t kRowSplit = 1u << 31;  // split_by_class's mark on a packed count
   // A key is split only below this many rows: the packed count |A| | |B| << 16 (|A| < |B|) then
   // stays below the mark, which build_index strips again

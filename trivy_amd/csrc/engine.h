@@ -409,7 +409,7 @@ class Engine {
   bool alloc_batch(const HostBatch& hb, DevBatch& b, std::string& err, bool pooled = false);
   bool upload(const HostBatch& hb, DevBatch& b, std::string& err);
   uint32_t grammar_set(const HostBatch& hb) const;
-  uint64_t scratch_words(const HostBatch& hb) const;
+  uint64_t scratch_words(const HostBatch& hb, int64_t* over_limit = nullptr) const;
   // Frees a batch's / a match list's device buffers (device = the GPU they live on; no
   // engine state is touched, so a batch outlives a hot swap of the engine's tables).
   static void free_batch(int device, DevBatch& b, bool pooled = false);

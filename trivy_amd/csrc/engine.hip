@@ -238,14 +238,34 @@ uint32_t batch_grammar_set(const DB& db, const HostBatch& hb) {
 
 // Scratch words a batch may need: keys longer than 32 bytes (the widest grammar's bound)
 // and, for Maven packages, the packed parse of the installed version (AUX_MVN rows).
-uint64_t Engine::scratch_words(const HostBatch& hb) const {
+//
+// over_limit: set to the first package whose version the batch cannot carry (else left alone).
+// An installed key's length travels in 14 bits (match_kernel.h KI_LEN), and HostBatch::add cuts
+// a version at 0xFFFF bytes; a key past the one or a text at the other would be compared as
+// something else, silently, so such a package is found here - the one host pass over every
+// package before a batch reaches the device - and the upload is refused.  Versions of at most
+// kVerLenFits bytes cannot reach the limit (key_bound_any); a longer one is encoded to see.
+uint64_t Engine::scratch_words(const HostBatch& hb, int64_t* over_limit) const {
   const auto& pi = db_->plat_info;
   std::atomic<uint64_t> total{0};
+  std::atomic<int64_t> over{-1};
+  constexpr uint32_t kVerLenFits = (KI_LEN - 24) / 5;
+  static_assert(5 * kVerLenFits + 24 <= KI_LEN, "key_bound_any(kVerLenFits) fits the length field");
   range_for(hb.pk.size(), 1 << 18, [&](size_t a, size_t b) {
     uint64_t w = 0;
     for (size_t i = a; i < b; i++) {
       const uint2 d = hb.pk[i];
       const uint32_t vlen = d.y >> 16;
+      if (vlen > kVerLenFits && d.x < pi.size()) {
+        const std::string_view v = hb.version(i);
+        CountSink cs;
+        uint32_t cls = 0;
+        if (vlen == 0xFFFF || (encode_version_cls(pi[d.x].cmp, reinterpret_cast<const uint8_t*>(v.data()), vlen, cs, cls) &&
+                               cs.n > KI_LEN)) {
+          int64_t cur = over.load(std::memory_order_relaxed);
+          while ((cur < 0 || int64_t(i) < cur) && !over.compare_exchange_weak(cur, int64_t(i))) {}
+        }
+      }
       const uint32_t need = (key_bound_any(vlen) + 7) / 8;
       const bool mvn = d.x < pi.size() && pi[d.x].cmp == CMP_MAVEN;
       if (need > (mvn ? 2u : kKeyWords)) w += need;  // Maven keys spill from 17 bytes (probe_one)
@@ -253,7 +273,16 @@ uint64_t Engine::scratch_words(const HostBatch& hb) const {
     }
     total.fetch_add(w, std::memory_order_relaxed);
   });
+  if (over_limit && over.load() >= 0) *over_limit = over.load();
   return total.load();
+}
+
+// The refusal of a batch whose package `i` has a version past the limits above.
+static std::string version_limit_error(const HostBatch& hb, int64_t i) {
+  return "package " + std::to_string(i) + " (" + std::string(hb.name(size_t(i)).substr(0, 64)) + "): a version of " +
+         std::to_string(hb.version(size_t(i)).size()) +
+         (hb.version(size_t(i)).size() >= 0xFFFF ? " bytes or more is not compared (limit 65534 bytes)"
+                                                 : " bytes has a sort key of more than 16383 bytes and is not compared");
 }
 
 bool Engine::alloc_batch(const HostBatch& hb, DevBatch& b, std::string& err, bool pooled) {
@@ -263,7 +292,12 @@ bool Engine::alloc_batch(const HostBatch& hb, DevBatch& b, std::string& err, boo
   b.n_tiles = hb.n_tiles();
   b.arena_bytes = hb.arena.size();
   b.gm = grammar_set(hb);
-  b.spill_words = scratch_words(hb);
+  int64_t over = -1;
+  b.spill_words = scratch_words(hb, &over);
+  if (over >= 0) {
+    err = version_limit_error(hb, over);
+    return false;
+  }
   if (!hb.attr.empty() && hb.attr.size() != hb.pk.size()) {
     err = "batch attributes do not cover every package";
     return false;
@@ -757,7 +791,7 @@ bool Engine::dropin_run(Dropin& d, DropinReq* const* reqs, size_t n, std::string
   b.n_tiles = hb.n_tiles();
   b.arena_bytes = hb.arena.size();
   b.gm = grammar_set(hb);
-  b.spill_words = scratch_words(hb);
+  b.spill_words = scratch_words(hb);  // match_host refused over-limit versions, call by call
   if (!hb.attr.empty() && hb.attr.size() != hb.pk.size()) {
     err = "batch attributes do not cover every package";
     return false;
@@ -877,6 +911,14 @@ bool Engine::match_host(const HostBatch& hb, std::vector<uint2>& out, int64_t& e
   out.clear();
   err_pkg = -1;
   if (hb.pk.empty()) return true;
+  // over-limit versions (scratch_words) are refused here, per call: concurrent calls run merged,
+  // and one caller's package must not fail the others
+  int64_t over = -1;
+  scratch_words(hb, &over);
+  if (over >= 0) {
+    err = version_limit_error(hb, over);
+    return false;
+  }
   Dropin* dp = dropin(err);
   if (!dp) return false;
   Dropin& d = *dp;
